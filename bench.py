@@ -17,6 +17,10 @@ n_gpus so the driver's multi-GPU run produces the complete headline:
 Launch (driver contract):
     python bench.py --gpus N --steps K --warmup W
 N>1 runs under torch.distributed.run with one rank per GPU over RCCL.
+Such a plain run measures only the shallow-water headline: K timed steps
+after W warm-up steps, one JSON line.  ``--full`` adds the communication
+configs above to that line; ``--dump-outputs DIR`` writes the state of
+the last timed step as ``DIR/<name>.npy``.
 
 ``--preflight`` instead validates the N>1 machinery end-to-end over the
 gloo bootstrap plane (CPU): decomposed model steps, cross-rank halo
@@ -248,6 +252,45 @@ def preflight():
     sys.exit(1 if all_fail else 0)
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # keeps the files under 64 MB in all
+DUMP_SAMPLE_SEED = 20240531
+
+
+def dump_outputs(sw, state, outdir):
+    """Write the model state the timed path returned from its last step
+    (h, u, v and the AB2 tendencies dh, du, dv) as ``outdir/<name>.npy``.
+
+    At world size 1 these are the local arrays, halo ring included; at
+    N>1 each field's interior is gathered onto rank 0, which writes it.
+    Arrays keep the model dtype (float32 here).  If the fields together
+    exceed the budget, every field is reduced to the same fixed, seeded
+    sample of its flattened elements (indices ascending), so two builds
+    run with the same arguments write comparable files."""
+    import numpy as np
+
+    fields = {}
+    for name in state._fields:
+        f = getattr(state, name)
+        if sw.comm.size > 1:
+            f = sw.gather_global(f)  # collective: every rank takes part
+        if f is not None:
+            fields[name] = f.detach().to("cpu").contiguous().numpy()
+    if sw.comm.rank != 0:
+        return
+    total = sum(a.nbytes for a in fields.values())
+    if total > DUMP_BUDGET_BYTES:
+        numel = next(iter(fields.values())).size
+        itemsize = max(a.itemsize for a in fields.values())
+        keep = DUMP_BUDGET_BYTES // (len(fields) * itemsize)
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = np.sort(rng.choice(numel, size=min(keep, numel),
+                                 replace=False))
+        fields = {k: a.reshape(-1)[idx] for k, a in fields.items()}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in fields.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -256,9 +299,16 @@ def main():
     p.add_argument("--nx", type=int, default=3600)
     p.add_argument("--ny", type=int, default=1800)
     p.add_argument("--preflight", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the shallow-water metric, also measure the "
+                        "BASELINE communication configs (off by default)")
     p.add_argument("--skip-comm-bench", action="store_true",
-                   help="only the shallow-water metric")
+                   help="only the shallow-water metric, even with --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's state as DIR/<name>.npy")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     if args.preflight:
         preflight()
@@ -318,14 +368,19 @@ def main():
     # 0.101 at spc=10); capture+validation cost stays untimed either way
     if args.steps >= 250:
         spc = 50
-    elif args.steps >= 10:
-        spc = args.steps if args.steps <= 50 else 10
+    elif args.steps > 50:
+        spc = 10
     else:
-        spc = max(args.steps, 1)
-    advance, state = sw.make_stepper(state, steps_per_call=spc)
-    advance()  # one warm replay
+        # graph capture needs an even step count (buffer parity); an odd
+        # --steps runs its last step through the plain step below
+        spc = args.steps - args.steps % 2
+    if spc:
+        advance, state = sw.make_stepper(state, steps_per_call=spc)
+        advance()  # one warm replay
+        n_calls, rem = divmod(args.steps, spc)
+    else:
+        n_calls, rem = 0, args.steps
 
-    n_calls, rem = divmod(args.steps, spc)
     m.barrier()
     if use_gpu:
         torch.cuda.synchronize()
@@ -351,8 +406,11 @@ def main():
     spd = sw.steps_per_model_day()
     sec_per_model_day = spd / steps_per_sec
 
+    if args.dump_outputs:
+        dump_outputs(sw, state, args.dump_outputs)
+
     comm_bench = {}
-    if use_gpu and not args.skip_comm_bench:
+    if args.full and use_gpu and not args.skip_comm_bench:
         for name, fn in (
             ("allreduce_256MiB_bf16", lambda: bench_allreduce_graph(comm)),
             ("bisection_1GiB_bf16",
