@@ -920,7 +920,7 @@ __device__ inline void st2s(float* p, long long off, vf2 v) {
 // the pair-fast predicate of the 2-column update kernels: matches
 // stage19_cells' fast branch exactly (the ld4 at idn reads offsets 0..3,
 // so the pair must keep i0+3 in-row)
-__device__ inline bool stage19_pair_fast(const SwArgs<float>& a, int j,
+__host__ __device__ inline bool stage19_pair_fast(const SwArgs<float>& a, int j,
                                          int i0) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int jmin = a.f.south_open ? 1 : 2;
@@ -1148,7 +1148,7 @@ constexpr int kFill30 = kTR30 * kTP30;     // LDS fill tasks
 // friction output (j, pair i0) is servable from the fast kernel iff the
 // nine (row, pair) LDS inputs it needs are all stage19-fast and the pair
 // is stage27-fast; folds to pure bounds:
-__device__ inline bool s30_fast_out(const SwArgs<float>& a, int j,
+__host__ __device__ inline bool s30_fast_out(const SwArgs<float>& a, int j,
                                     int i0) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int jmin = a.f.south_open ? 1 : 2;
@@ -1354,6 +1354,375 @@ __global__ void sw_stage30_ringB(SwArgs<float> a) {
   a.v2[idx] = vv2;
 }
 
+// ------------------------------------- stage 30/31: single-launch step
+// World-1 form of the fused step: ONE kernel writes everything the fast
+// kernel + ringA + ringB write, with no fe/fn staging and no dependency
+// between workgroups.  The three-launch shape exists only to ferry the
+// boundary strip's u'/v' between blocks; here a boundary tile fills its
+// own LDS apron by the per-cell rules s30_read_uv encodes (interior
+// non-fast cell -> stage8_math, closed halo -> pre-update field, x_wrap
+// halo -> the u'/v' of its wrap source, computed in place), so the ring
+// friction reads LDS like the fast friction does.  Requires fully-local
+// halos (every open halo is an x_wrap halo) — the plan only selects it
+// at world size 1; stages 32/33 keep the exchange shape.
+//
+// Tiles are of two block-uniform flavours.  FAST tiles (every fill pair
+// stage19_pair_fast, every output pair s30_fast_out) run the two vector
+// passes only.  PERIMETER tiles run the same vector passes over their
+// fast pairs, then a scalar pass over the few remaining cells, which
+// are enumerated compactly (the complement of the fast rectangle inside
+// the tile) so no wave of mostly-fast pairs diverges into scalar code.
+// Ownership of every store stays predicate-defined; the enumeration only
+// decides which threads look.
+
+// the fast tiles form a rectangle [tr0, tr1] x [tc0, tc1] of the tile
+// grid (both predicates are pure bounds); host and device share this
+struct S1Tiles {
+  int bpc, bands, tr0, tr1, tc0, tc1, nfast, nper, nper_pad;
+};
+
+__host__ __device__ inline int s1_floordiv(int x, int d) {
+  return x >= 0 ? x / d : -((-x + d - 1) / d);
+}
+
+__host__ __device__ inline S1Tiles s1_tiles(int ny, int nx,
+                                            const SwFlags& f) {
+  const int jmin = f.south_open ? 1 : 2;
+  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
+  const int imin = f.west_open ? 1 : 2;
+  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  S1Tiles t;
+  t.bpc = (nx + 2 * kPC30 - 1) / (2 * kPC30);
+  t.bands = (ny + kTJ30 - 1) / kTJ30;
+  // rows jb-1 .. jb+TJ all stage19-fast; pairs cb-2 .. cb+2*PC all
+  // stage19-fast (i0 + 2 <= imax, i0 + 3 < nx at the last fill pair)
+  t.tr0 = s1_floordiv(jmin + 1 + kTJ30 - 1, kTJ30);
+  t.tr1 = s1_floordiv(jmax - kTJ30, kTJ30);
+  t.tc0 = s1_floordiv(imin + 2 + 2 * kPC30 - 1, 2 * kPC30);
+  const int ihi = imax - 2 < nx - 4 ? imax - 2 : nx - 4;
+  t.tc1 = s1_floordiv(ihi - 2 * kPC30, 2 * kPC30);
+  if (t.tr1 > t.bands - 1) t.tr1 = t.bands - 1;
+  if (t.tc1 > t.bpc - 1) t.tc1 = t.bpc - 1;
+  const bool any = t.tr0 <= t.tr1 && t.tc0 <= t.tc1;
+  t.nfast = any ? (t.tr1 - t.tr0 + 1) * (t.tc1 - t.tc0 + 1) : 0;
+  if (!any) {  // canonical empty rectangle: every band is a "top" band
+    t.tr0 = t.bands;
+    t.tr1 = t.bands - 1;
+    t.tc0 = 0;
+    t.tc1 = -1;
+  }
+  t.nper = t.bpc * t.bands - t.nfast;
+  // the dispatcher deals blocks to XCDs by raw id mod 8: pad so the fast
+  // tiles' XCD bands start on a multiple of 8
+  t.nper_pad = (t.nper + 7) / 8 * 8;
+  return t;
+}
+
+// block id -> tile.  Perimeter tiles take the lowest block ids, so their
+// longer scalar chains overlap the bulk instead of forming a tail; the
+// fast tiles keep the XCD-band remap over their own rectangle.  Returns
+// 0 for a padding block, 1 for a perimeter tile, 2 for a fast tile.
+__host__ __device__ inline int s1_block_tile(const S1Tiles& tl, int b,
+                                             int* tr, int* tc) {
+  if (b < tl.nper_pad) {
+    if (b >= tl.nper) return 0;
+    const int top = tl.tr0 * tl.bpc;
+    const int bot = (tl.bands - 1 - tl.tr1) * tl.bpc;
+    if (b < top) {
+      *tr = b / tl.bpc;
+      *tc = b % tl.bpc;
+    } else if (b < top + bot) {
+      *tr = tl.tr1 + 1 + (b - top) / tl.bpc;
+      *tc = (b - top) % tl.bpc;
+    } else {
+      const int w = tl.tc0 + (tl.bpc - 1 - tl.tc1);
+      const int u = b - top - bot, c = u % w;
+      *tr = tl.tr0 + u / w;
+      *tc = c < tl.tc0 ? c : tl.tc1 + 1 + (c - tl.tc0);
+    }
+    return 1;
+  }
+  const int T_ = tl.nfast;
+  const int f_ = b - tl.nper_pad;
+  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = f_ % 8, yc_ = f_ / 8;
+  const int bid_ =
+      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
+      + yc_;
+  const int fw = tl.tc1 - tl.tc0 + 1;
+  *tr = tl.tr0 + bid_ / fw;
+  *tc = tl.tc0 + bid_ % fw;
+  return 2;
+}
+
+// a tile's fast cells as a local rectangle: rows [r0, r1] x cols
+// [c0, c1] of an R-row x 2P-column grid, from the first/last fast local
+// row and pair (unclamped); empty = (r0 = R, r1 = R - 1, c0 = 0, c1 = -1)
+struct S1Rect {
+  int r0, r1, c0, c1;
+};
+
+__host__ __device__ inline S1Rect s1_clip_rect(int r0, int r1, int p0,
+                                               int p1, int R, int P) {
+  if (r0 < 0) r0 = 0;
+  if (r1 > R - 1) r1 = R - 1;
+  if (p0 < 0) p0 = 0;
+  if (p1 > P - 1) p1 = P - 1;
+  if (r0 > r1 || p0 > p1) return {R, R - 1, 0, -1};
+  return {r0, r1, 2 * p0, 2 * p1 + 1};
+}
+
+// stage19_pair_fast over the (TJ+2) x 2(PC+2) fill grid of tile (jb, cb)
+__host__ __device__ inline S1Rect s1_fill_rect(int ny, int nx,
+                                               const SwFlags& f, int jb,
+                                               int cb) {
+  const int jmin = f.south_open ? 1 : 2;
+  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
+  const int imin = f.west_open ? 1 : 2;
+  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  const int ihi = imax - 2 < nx - 4 ? imax - 2 : nx - 4;
+  return s1_clip_rect(jmin - (jb - 1), jmax - (jb - 1),
+                      s1_floordiv(imin - (cb - 2) + 1, 2),
+                      s1_floordiv(ihi - (cb - 2), 2), kTR30, kTP30);
+}
+
+// s30_fast_out over the TJ x 2PC output grid of tile (jb, cb)
+__host__ __device__ inline S1Rect s1_out_rect(int ny, int nx,
+                                              const SwFlags& f, int jb,
+                                              int cb) {
+  const int jmin = f.south_open ? 1 : 2;
+  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
+  const int imin = f.west_open ? 1 : 2;
+  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  const int ohi = imax - 4 < nx - 6 ? imax - 4 : nx - 6;
+  return s1_clip_rect(jmin + 1 - jb, jmax - 1 - jb,
+                      s1_floordiv(imin + 2 - cb + 1, 2),
+                      s1_floordiv(ohi - cb, 2), kTJ30, kPC30);
+}
+
+// k-th cell of the complement of rectangle [r0, r1] x [c0, c1] inside an
+// R x C grid (rows above, rows below, then the left/right strips of the
+// middle rows).  Empty rectangle = (r0 = R, r1 = R - 1).
+__host__ __device__ inline int s1_rim_count(int R, int C, int r0, int r1, int c0,
+                                   int c1) {
+  return (r0 + (R - 1 - r1)) * C + (r1 - r0 + 1) * (c0 + (C - 1 - c1));
+}
+
+__host__ __device__ inline void s1_rim_cell(int k, int R, int C, int r0, int r1,
+                                   int c0, int c1, int* ro, int* co) {
+  const int full = (r0 + (R - 1 - r1)) * C;
+  if (k < full) {
+    const int r = k / C;
+    *ro = r < r0 ? r : r1 + 1 + (r - r0);
+    *co = k % C;
+  } else {
+    const int w = c0 + (C - 1 - c1);
+    const int u = k - full;
+    const int c = u % w;
+    *ro = r0 + u / w;
+    *co = c < c0 ? c : c1 + 1 + (c - c0);
+  }
+}
+
+// x + dt * (aa * dn + ab * dold) rounded as: two products, their sum,
+// one FMA into x — independent of how the call site gets optimized
+__device__ inline float s1_ab_update(float x, float dt, float aa, float dn,
+                                     float ab, float dold) {
+#pragma clang fp contract(off)
+  const float p = aa * dn;
+  const float q = ab * dold;
+  const float s = p + q;
+  return __builtin_fmaf(dt, s, x);
+}
+
+template <int NT_>
+__global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
+  const int ny = (int)a.ny, nx = (int)a.nx;
+  const S1Tiles tl = s1_tiles(ny, nx, a.f);
+  const int b_ = (int)blockIdx.x;
+  int tr, tc;
+  const int flavour = s1_block_tile(tl, b_, &tr, &tc);
+  if (flavour == 0) return;  // padding block
+  const bool perim = flavour == 1;
+  const int jb = tr * kTJ30;       // first owned output row
+  const int cb = tc * 2 * kPC30;   // first owned output column
+  const int tid = (int)threadIdx.x;
+
+  __shared__ float su[kTR30][2 * kTP30], sv[kTR30][2 * kTP30];
+
+  // pass 1, vector: the stage-19 update of every fast pair of the tile
+  for (int t = tid; t < kFill30; t += NT_) {
+    const int lr = t / kTP30, lp = t % kTP30;
+    const int rr = jb - 1 + lr;
+    const int i0 = cb - 2 + 2 * lp;
+    if (rr < 0 || !stage19_pair_fast(a, rr, i0)) continue;
+    Upd2 w = stage19_math<false>(a, rr, i0);
+    su[lr][2 * lp] = w.uu.x;
+    su[lr][2 * lp + 1] = w.uu.y;
+    sv[lr][2 * lp] = w.vv.x;
+    sv[lr][2 * lp + 1] = w.vv.y;
+    if (lr >= 1 && lr <= kTJ30 && lp >= 1 && lp <= kPC30) {
+      const long long idx = (long long)rr * nx + i0;  // owned pair
+      st2(a.dnh, idx, w.dnh);
+      st2(a.dnu, idx, w.dnu);
+      st2(a.dnv, idx, w.dnv);
+      st2(a.h2, idx, w.hh);
+    }
+  }
+
+  if (perim) {
+    // pass 1, scalar: every in-domain tile cell that is not part of a
+    // fast pair.  The fast pairs of the tile are the local rectangle
+    // rows [r0, r1] x cols [c0, c1]; its complement is enumerated.
+    const S1Rect fr = s1_fill_rect(ny, nx, a.f, jb, cb);
+    const int r0 = fr.r0, r1 = fr.r1, c0 = fr.c0, c1 = fr.c1;
+    const int nrim = s1_rim_count(kTR30, 2 * kTP30, r0, r1, c0, c1);
+#pragma unroll 1
+    for (int k = tid; k < nrim; k += NT_) {
+      int lr, lc;
+      s1_rim_cell(k, kTR30, 2 * kTP30, r0, r1, c0, c1, &lr, &lc);
+      const int rr = jb - 1 + lr, ii = cb - 2 + lc;
+      if (rr < 0 || rr >= ny || ii < 0 || ii >= nx) continue;
+      if (stage19_pair_fast(a, rr, ii & ~1)) continue;  // vector pass did it
+      // the cell whose u'/v' this entry holds: itself, or its wrap source
+      int is = ii;
+      if (a.f.x_wrap) {
+        if (ii == 0) is = nx - 2;
+        else if (ii == nx - 1) is = 1;
+      }
+      const long long sdx = (long long)rr * nx + is;
+      if (rr < 1 || rr > ny - 2 || is < 1 || is > nx - 2) {
+        su[lr][lc] = a.u[sdx];  // closed halo: pre-update pass-through
+        sv[lr][lc] = a.v[sdx];
+        continue;
+      }
+      CellUpd<float> r8 = stage8_math(a, rr, is);
+      // the AB time update, with ringA's rounding spelled out: there the
+      // compiler packs the two products of x + dt*(ab_a*dn + ab_b*do)
+      // into one v_pk_mul (no FMA between them); here it would sink the
+      // h update into the owned-cell branch and contract it, and the two
+      // paths would differ by an ulp of h every few steps
+      r8.hh = s1_ab_update(a.h[sdx], a.dt, a.ab_a, r8.dnh, a.ab_b,
+                           a.doh[sdx]);
+      r8.uu = s1_ab_update(a.u[sdx], a.dt, a.ab_a, r8.dnu, a.ab_b,
+                           a.dou[sdx]);
+      r8.vv = s1_ab_update(a.v[sdx], a.dt, a.ab_a, r8.dnv, a.ab_b,
+                           a.dov[sdx]);
+      if (a.f.east_wall && is == nx - 2) r8.uu = 0.f;
+      if (a.f.north_wall && rr == ny - 2) r8.vv = 0.f;
+      su[lr][lc] = r8.uu;
+      sv[lr][lc] = r8.vv;
+      if (is == ii && lr >= 1 && lr <= kTJ30 && lc >= 2 &&
+          lc <= 2 * kPC30 + 1) {  // owned interior cell
+        a.dnh[sdx] = r8.dnh;
+        a.dnu[sdx] = r8.dnu;
+        a.dnv[sdx] = r8.dnv;
+        a.h2[sdx] = r8.hh;
+        if (a.f.x_wrap) {  // owner of a wrap source refreshes its halo
+          if (ii == nx - 2) a.h2[(long long)rr * nx] = r8.hh;
+          if (ii == 1) a.h2[(long long)rr * nx + nx - 1] = r8.hh;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // pass 2, vector: friction of the fast output pairs from LDS
+  for (int t = tid; t < kTJ30 * kPC30; t += NT_) {
+    const int ro = t / kPC30, po = t % kPC30;
+    const int j = jb + ro;
+    const int i0 = cb + 2 * po;
+    if (!s30_fast_out(a, j, i0)) continue;  // scalar pass owns this pair
+    const int lr = ro + 1, x = 2 * po + 2;
+    const long long idx = (long long)j * nx + i0;
+    // stage27_pair math, inputs from LDS
+    vf2 uw = {su[lr][x - 1], su[lr][x]}, uc = {su[lr][x], su[lr][x + 1]},
+        ue = {su[lr][x + 1], su[lr][x + 2]};
+    vf2 un = {su[lr + 1][x], su[lr + 1][x + 1]},
+        us = {su[lr - 1][x], su[lr - 1][x + 1]};
+    vf2 vw = {sv[lr][x - 1], sv[lr][x]}, vcc = {sv[lr][x], sv[lr][x + 1]},
+        ve = {sv[lr][x + 1], sv[lr][x + 2]};
+    vf2 vn = {sv[lr + 1][x], sv[lr + 1][x + 1]},
+        vs = {sv[lr - 1][x], sv[lr - 1][x + 1]};
+    const float nu = a.nu;
+    vf2 lu = (nu * (ue - uc) * a.rdx - nu * (uc - uw) * a.rdx) * a.rdx +
+             (nu * (un - uc) * a.rdy - nu * (uc - us) * a.rdy) * a.rdy;
+    vf2 lv = (nu * (ve - vcc) * a.rdx - nu * (vcc - vw) * a.rdx) * a.rdx +
+             (nu * (vn - vcc) * a.rdy - nu * (vcc - vs) * a.rdy) * a.rdy;
+    st2(a.u2, idx, uc + a.dt * lu);
+    st2(a.v2, idx, vcc + a.dt * lv);
+  }
+
+  if (perim) {
+    // pass 2, scalar: owned cells outside the s30_fast_out rectangle —
+    // ringb_final_uv's friction (division form, wall masks) with the
+    // five inputs from LDS, plus the halo cells' end-of-step values
+    const S1Rect orc = s1_out_rect(ny, nx, a.f, jb, cb);
+    const int r0 = orc.r0, r1 = orc.r1, c0 = orc.c0, c1 = orc.c1;
+    const int nrim = s1_rim_count(kTJ30, 2 * kPC30, r0, r1, c0, c1);
+#pragma unroll 1
+    for (int k = tid; k < nrim; k += NT_) {
+      int ro, co;
+      s1_rim_cell(k, kTJ30, 2 * kPC30, r0, r1, c0, c1, &ro, &co);
+      const int j = jb + ro, i = cb + co;
+      if (j >= ny || i >= nx) continue;
+      if (s30_fast_out(a, j, i & ~1)) continue;  // vector pass did it
+      const long long idx = (long long)j * nx + i;
+      if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
+        // halo cell.  An x_wrap halo of an interior row is refreshed by
+        // the owner of its wrap source (below); every other halo cell
+        // passes the pre-update field through (x-wrapped at corners)
+        int is = i;
+        if (a.f.x_wrap) {
+          if (i == 0) is = nx - 2;
+          else if (i == nx - 1) is = 1;
+        }
+        if (is != i && j >= 1 && j <= ny - 2) continue;
+        const long long sdx = (long long)j * nx + is;
+        a.h2[idx] = a.h[sdx];
+        a.u2[idx] = a.u[sdx];
+        a.v2[idx] = a.v[sdx];
+        continue;
+      }
+      const int lr = ro + 1, x = co + 2;
+      const float uc = su[lr][x], vc = sv[lr][x];
+      const float un = su[lr + 1][x], vn = sv[lr + 1][x];
+      const float us = su[lr - 1][x], vs = sv[lr - 1][x];
+      const float ue = su[lr][x + 1], ve = sv[lr][x + 1];
+      const float uw = su[lr][x - 1], vw = sv[lr][x - 1];
+      auto gu = [&](float c, float e, int ii) -> float {
+        if (ii > nx - 2 || (ii == 0 && !a.f.west_open)) return 0.f;
+        if (a.f.east_wall && ii == nx - 2) return 0.f;
+        return a.nu * (e - c) / a.dx;
+      };
+      auto gv = [&](float c, float n, int jj) -> float {
+        if (jj > ny - 2 || (jj == 0 && !a.f.south_open)) return 0.f;
+        if (a.f.north_wall && jj == ny - 2) return 0.f;
+        return a.nu * (n - c) / a.dy;
+      };
+      const float lu = (gu(uc, ue, i) - gu(uw, uc, i - 1)) / a.dx +
+                       (gv(uc, un, j) - gv(us, uc, j - 1)) / a.dy;
+      const float lv = (gu(vc, ve, i) - gu(vw, vc, i - 1)) / a.dx +
+                       (gv(vc, vn, j) - gv(vs, vc, j - 1)) / a.dy;
+      float uu2 = uc + a.dt * lu;
+      float vv2 = vc + a.dt * lv;
+      if (a.f.east_wall && i == nx - 2) uu2 = 0.f;
+      if (a.f.north_wall && j == ny - 2) vv2 = 0.f;
+      a.u2[idx] = uu2;
+      a.v2[idx] = vv2;
+      if (a.f.x_wrap) {  // owner of a wrap source refreshes its halo
+        if (i == nx - 2) {
+          a.u2[(long long)j * nx] = uu2;
+          a.v2[(long long)j * nx] = vv2;
+        }
+        if (i == 1) {
+          a.u2[(long long)j * nx + nx - 1] = uu2;
+          a.v2[(long long)j * nx + nx - 1] = vv2;
+        }
+      }
+    }
+  }
+}
+
 
 int sw_grid(long long n) {
   long long blocks = (n + kBlock - 1) / kBlock;
@@ -1443,18 +1812,25 @@ void launch_sw_stage(int stage, const SwLaunchParams& p, int is_double,
       case 23: hipLaunchKernelGGL(sw_stage21t<16>, grid, block, 0, stream, a); break;
       case 27: hipLaunchKernelGGL(sw_stage27v, grid, block, 0, stream, a); break;
       case 30:
-      case 31:    // 31 = 512-thread blocks (single-round LDS fill)
+      case 31: {  // the whole world-1 step in one launch; 31 = 512-thread
+                  // blocks (single-round LDS fill), same per-task code
+        const S1Tiles tl = s1_tiles((int)p.ny, (int)p.nx, a.f);
+        dim3 g1((unsigned)(tl.nper_pad + tl.nfast));
+        if (stage == 31) {
+          hipLaunchKernelGGL(sw_step1t<512>, g1, dim3(512), 0, stream, a);
+        } else {
+          hipLaunchKernelGGL(sw_step1t<256>, g1, block, 0, stream, a);
+        }
+        break;
+      }
+      case 34:    // 34 = the three-launch world-1 form (fast + ringA +
+                  // ringB through the fe/fn strip), kept for A/B runs
       case 32: {  // 32 = fast + ringA only (N>1: a real fe/fn halo
                   // exchange runs before ringB, launched as stage 33)
         long long bpc = (p.nx + 2 * kPC30 - 1) / (2 * kPC30);
         long long bands = (p.ny + kTJ30 - 1) / kTJ30;
         dim3 g30((unsigned)(bpc * bands));
-        if (stage == 31) {
-          hipLaunchKernelGGL(sw_stage30t<512>, g30, dim3(512), 0, stream,
-                             a);
-        } else {
-          hipLaunchKernelGGL(sw_stage30t<256>, g30, block, 0, stream, a);
-        }
+        hipLaunchKernelGGL(sw_stage30t<256>, g30, block, 0, stream, a);
         long long er = p.ny < 8 ? p.ny : 8, ec = p.nx < 12 ? p.nx : 12;
         long long ring = er * p.nx +
                          (p.ny > 8 ? (p.ny - 8) * ec : 0);

@@ -14,10 +14,11 @@ day is the headline metric.
 
 Two step implementations share semantics: an eager torch-op path (CPU
 and reference/debugging) and the fused MI355X path — by default ONE
-LDS-tiled update+friction pass plus two boundary-ring kernels (stage
-30/32; at world 1 the ring kernel also writes the periodic wrap refresh,
-so a whole model step launches zero exchange kernels; multi-rank, a
-two-field u'/v'-strip exchange runs between the ring kernels), with the
+LDS-tiled update+friction pass (stage 30: at world 1 a single kernel
+launch is the whole model step, boundary tiles and the periodic wrap
+refresh included, with zero exchange kernels; stage 32, multi-rank: the
+pass plus two boundary-ring kernels with a two-field u'/v'-strip
+exchange between them), with the
 two-kernel pipeline (stage 19 tendencies+update, stage 27 friction,
 selectable variants and scalar fallbacks) behind MPI4JAX_AMD_SW_NOFUSE,
 a one-native-call halo exchange (merged pack launch, single RCCL group,
@@ -275,16 +276,22 @@ class ShallowWater:
             if (self.lateral_viscosity > 0
                     and not os.environ.get("MPI4JAX_AMD_SW_OVERLAP")
                     and os.environ.get("MPI4JAX_AMD_SW_NOFUSE") != "1"):
-                # update+friction fused (stage 30 fast kernel + boundary
-                # ring kernels) — drops the u'/v' intermediate round
-                # trip (4 of 16 field passes); equivalent to the
+                # update+friction fused — drops the u'/v' intermediate
+                # round trip (4 of 16 field passes); equivalent to the
                 # two-kernel path to FMA-contraction rounding
                 # (tests/test_gpu_ops.py::test_stage30_*).  s7=None
-                # marks the world-1 shape (in-kernel wrap refresh, zero
-                # exchange launches); s7=33 the multi-rank shape (a real
-                # fe/fn strip exchange between ringA and ringB).
+                # marks the world-1 shape: the whole step is ONE kernel
+                # launch (boundary tiles recompute their own u'/v'
+                # apron, in-kernel wrap refresh, zero exchange
+                # launches); MPI4JAX_AMD_SW_RING3=1 selects the earlier
+                # three-launch form (fast + ringA + ringB through the
+                # fe/fn strip) for A/B measurement.  s7=33 is the
+                # multi-rank shape (a real fe/fn strip exchange between
+                # ringA and ringB).
                 if (self.grid.nproc_y * self.grid.nproc_x == 1
                         and not self._force_remote_exchange):
+                    if os.environ.get("MPI4JAX_AMD_SW_RING3") == "1":
+                        return None, 34, None  # three-launch form
                     if os.environ.get("MPI4JAX_AMD_SW_FUSE512") == "1":
                         return None, 31, None  # 512-thread variant
                     return None, 30, None
@@ -326,11 +333,12 @@ class ShallowWater:
 
         if s1 is not None:
             stage(s1)     # fe, fn, q, ke (with open-edge halo formulas)
-        if s6 in (30, 31):
+        if s6 in (30, 31, 34):
             # fused update+friction: u'/v' never round-trip through HBM,
-            # the mid-step exchange disappears, and the ring kernel
-            # writes the end-of-step wrap refresh itself — a complete
-            # model step with zero exchange launches
+            # the mid-step exchange disappears, and the kernel writes
+            # the end-of-step wrap refresh itself — a complete model
+            # step with zero exchange launches (30/31: one launch; 34:
+            # the three-launch form)
             stage(s6)
             self._swap("h", "u", "v")
             for k in ("h", "u", "v"):
