@@ -918,6 +918,180 @@ void sw_exchange(std::vector<at::Tensor> fields,
   watchdog_arm("sw_exchange", c.rank, stream);
 }
 
+// Native executor of parallel/halo.HaloExchanger: one pack launch, one
+// RCCL group, one unpack launch, for `levels` x (ny, nx) fields with a
+// `width`-cell halo.  Entry i of send_to / recv_from (-1 = no peer) is
+// direction i of halo.DIRECTIONS: W, E, N, S, then the diagonals
+// (-1,-1), (-1,1), (1,-1), (1,1) as (dy, dx).  The strip sent toward
+// direction d is the interior strip next to edge d; the strip received
+// from -d lands in the halo at edge -d.  Column strips are full height,
+// row strips cover the interior columns, corner blocks are width x width.
+// Slot i of both staging buffers holds message i as
+// [field][level][row][col]; slot offsets are fixed by the geometry alone,
+// and computed identically by halo.py's Python executor.  Bit i of
+// local_mask marks a self-peer entry: it is packed straight into slot i
+// of the RECEIVE buffer and never enters the group.  Messages travel as
+// raw bytes, so any dtype of a supported element size is exchanged.
+void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
+                      int64_t ny, int64_t nx, int64_t width,
+                      std::vector<int64_t> send_to,
+                      std::vector<int64_t> recv_from, int64_t local_mask,
+                      at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_exchange_nd");
+  const int64_t nf = (int64_t)fields.size();
+  TORCH_CHECK(1 <= nf && nf <= kHaloMaxFields, "1..", kHaloMaxFields,
+              " halo fields supported, got ", nf);
+  TORCH_CHECK(send_to.size() == kHaloDirs && recv_from.size() == kHaloDirs,
+              "halo_exchange_nd expects 8 send and 8 recv peers");
+  const int64_t w = width;
+  TORCH_CHECK(w >= 1 && levels >= 1 && ny >= 3 * w && nx >= 3 * w,
+              "bad halo geometry: levels ", levels, ", ny ", ny, ", nx ", nx,
+              ", width ", w, " (each axis needs n >= 3*width)");
+  TORCH_CHECK(levels < ((int64_t)1 << 31) && ny < ((int64_t)1 << 31) &&
+                  nx < ((int64_t)1 << 31),
+              "halo extents must be below 2^31");
+  const at::Tensor& f0 = fields[0];
+  const int64_t esz = f0.element_size();
+  TORCH_CHECK(esz == 1 || esz == 2 || esz == 4 || esz == 8,
+              "halo exchange supports 1/2/4/8-byte elements, got ", esz);
+  TORCH_CHECK(levels <= f0.numel() && f0.numel() / levels == ny * nx &&
+                  f0.numel() % levels == 0,
+              "halo field has ", f0.numel(), " elements, expected ", levels,
+              " x ", ny, " x ", nx);
+  HaloNdArgs pk{}, un{};
+  for (int64_t k = 0; k < nf; ++k) {
+    const auto& f = fields[k];
+    TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
+                    f.numel() == f0.numel() &&
+                    f.scalar_type() == f0.scalar_type() &&
+                    f.device() == f0.device(),
+                "bad halo field ", k);
+    pk.f[k] = un.f[k] = f.data_ptr();
+  }
+
+  // slot geometry: [0] columns W/E, [2] rows N/S, [4] corners
+  const int64_t dirs[kHaloDirs][2] = {{0, -1}, {0, 1},  {1, 0},  {-1, 0},
+                                      {-1, -1}, {-1, 1}, {1, -1}, {1, 1}};
+  int64_t slot_off[kHaloDirs + 1];
+  int64_t sy[kHaloDirs], sx[kHaloDirs], ry[kHaloDirs], rx[kHaloDirs];
+  int64_t hh[kHaloDirs], ww[kHaloDirs];
+  slot_off[0] = 0;
+  for (int i = 0; i < kHaloDirs; ++i) {
+    const int64_t dy = dirs[i][0], dx = dirs[i][1];
+    // y: a column strip (dy == 0) is full height
+    sy[i] = dy < 0 ? w : (dy > 0 ? ny - 2 * w : 0);
+    ry[i] = dy < 0 ? ny - w : 0;
+    hh[i] = dy != 0 ? w : ny;
+    // x: a row strip (dx == 0) covers the interior columns
+    sx[i] = dx < 0 ? w : (dx > 0 ? nx - 2 * w : w);
+    rx[i] = dx < 0 ? nx - w : (dx > 0 ? 0 : w);
+    ww[i] = dx != 0 ? w : nx - 2 * w;
+    slot_off[i + 1] = slot_off[i] + nf * levels * hh[i] * ww[i];
+  }
+  const int64_t total = slot_off[kHaloDirs];
+  TORCH_CHECK(total < ((int64_t)1 << 31),
+              "halo staging of ", total, " elements exceeds 2^31");
+  for (const at::Tensor* b : {&sbuf, &rbuf}) {
+    TORCH_CHECK(b->is_cuda() && b->is_contiguous() &&
+                    b->device() == f0.device() &&
+                    b->element_size() == esz && b->numel() >= total,
+                "bad halo staging buffer (need ", total, " elements of ",
+                esz, " bytes on the fields' device)");
+  }
+  TORCH_CHECK(0 <= local_mask && local_mask < (1 << kHaloDirs),
+              "bad halo local mask");
+
+  bool any_remote = false;
+  auto is_local = [&](int i) { return (local_mask >> i) & 1; };
+  for (int i = 0; i < kHaloDirs; ++i) {
+    TORCH_CHECK(send_to[i] >= -1 && recv_from[i] >= -1, "bad halo peer");
+    if (is_local(i)) {
+      TORCH_CHECK(send_to[i] >= 0 && recv_from[i] >= 0,
+                  "local halo entry ", i, " needs both peers");
+    } else {
+      any_remote |= send_to[i] >= 0 || recv_from[i] >= 0;
+    }
+  }
+
+  char* sb = (char*)sbuf.data_ptr();
+  char* rb = (char*)rbuf.data_ptr();
+  auto fill_common = [&](HaloNdArgs& a) {
+    a.ny = ny;
+    a.nx = nx;
+    a.levels = (unsigned)levels;
+    a.nf = (int)nf;
+    a.w = (int)w;
+  };
+  fill_common(pk);
+  fill_common(un);
+  auto add_seg = [&](HaloNdArgs& a, int& n, unsigned& pos, int i, char* base,
+                     int64_t y0, int64_t x0) {
+    HaloNdSeg& s = a.seg[n++];
+    s.buf = base + slot_off[i] * esz;
+    s.y0 = y0;
+    s.x0 = x0;
+    s.h = (unsigned)hh[i];
+    s.wd = (unsigned)ww[i];
+    s.start = pos;
+    pos += (unsigned)(slot_off[i + 1] - slot_off[i]);
+    s.end = pos;
+    s.skip_lo = s.skip_hi = 0;
+  };
+  int npk = 0, nun = 0;
+  unsigned pk_pos = 0, un_pos = 0;
+  for (int i = 0; i < kHaloDirs; ++i) {
+    if (send_to[i] >= 0) {
+      add_seg(pk, npk, pk_pos, i, is_local(i) ? rb : sb, sy[i], sx[i]);
+    }
+    if (recv_from[i] >= 0) {
+      add_seg(un, nun, un_pos, i, rb, ry[i], rx[i]);
+      if (i < 2) {
+        // column strip with x-direction dx: its low rows [0, w) are the
+        // receive block of diagonal (+1, dx), its high rows of (-1, dx);
+        // a present corner segment owns them ("corners win")
+        const int lo = i == 0 ? 6 : 7, hi = i == 0 ? 4 : 5;
+        un.seg[nun - 1].skip_lo = recv_from[lo] >= 0;
+        un.seg[nun - 1].skip_hi = recv_from[hi] >= 0;
+      }
+    }
+  }
+  pk.total = pk_pos;
+  un.total = un_pos;
+  for (int i = npk; i < kHaloDirs; ++i) pk.seg[i].end = pk.total;
+  for (int i = nun; i < kHaloDirs; ++i) un.seg[i].end = un.total;
+
+  hipStream_t stream = cur_stream();
+  launch_halo_nd(pk, 0, (int)esz, stream);
+
+  if (any_remote) {
+    auto c = get_comm(comm_id);
+    for (int i = 0; i < kHaloDirs; ++i) {
+      TORCH_CHECK(send_to[i] < c.size && recv_from[i] < c.size,
+                  "halo peer out of range for communicator of size ",
+                  c.size);
+    }
+    log_enqueue("HaloExchangeNd", c, total);
+    RCCL_CHECK(ncclGroupStart());
+    for (int i = 0; i < kHaloDirs; ++i) {
+      if (is_local(i)) continue;
+      const int64_t nbytes = (slot_off[i + 1] - slot_off[i]) * esz;
+      if (send_to[i] >= 0) {
+        p2p_send(sb + slot_off[i] * esz, nbytes, ncclUint8, 1,
+                 (int)send_to[i], c.comm, stream);
+      }
+      if (recv_from[i] >= 0) {
+        p2p_recv(rb + slot_off[i] * esz, nbytes, ncclUint8, 1,
+                 (int)recv_from[i], c.comm, stream);
+      }
+    }
+    RCCL_CHECK(ncclGroupEnd());
+    launch_halo_nd(un, 1, (int)esz, stream);
+    watchdog_arm("halo_exchange_nd", c.rank, stream);
+  } else {
+    launch_halo_nd(un, 1, (int)esz, stream);
+  }
+}
+
 // direct access to the combine kernel (used by gpu numerics tests)
 void combine(at::Tensor dst, at::Tensor a, at::Tensor b, int64_t op) {
   check_pair(dst, a);
@@ -972,4 +1146,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sw_exchange", &sw_exchange);
   m.def("pack_halo", &pack_halo);
   m.def("unpack_halo", &unpack_halo);
+  m.def("halo_exchange_nd", &halo_exchange_nd);
 }

@@ -96,3 +96,35 @@ void launch_unpack_halo(void* const* fields, int nf, long long ny,
                         long long nx, void* cb0, long long c0, void* cb1,
                         long long c1, void* cor, int cor_mask,
                         int is_double, hipStream_t stream);
+
+// N-d halo staging for parallel/halo.HaloExchanger (halo.hip).  One launch
+// moves up to kHaloDirs segments; each segment is a (h, wd) window of
+// every level of every field, laid out [field][level][row][col] in its
+// staging slot.  Segments are compacted to the front; unused ones carry
+// end == total.  skip_lo / skip_hi (unpack only) make a full-height column
+// strip leave its first / last `w` rows to a corner segment of the same
+// launch.  Staging indices are 32-bit (total < 2^31, checked by the
+// caller); offsets into a field are 64-bit.
+constexpr int kHaloMaxFields = 8;
+constexpr int kHaloDirs = 8;
+
+struct HaloNdSeg {
+  void* buf;             // this segment's staging slot
+  long long y0, x0;      // window origin inside a (ny, nx) level
+  unsigned h, wd;        // window size
+  unsigned start, end;   // work-item range [start, end) of this segment
+  int skip_lo, skip_hi;
+};
+
+struct HaloNdArgs {
+  void* f[kHaloMaxFields];
+  HaloNdSeg seg[kHaloDirs];
+  long long ny, nx;
+  unsigned levels, total;
+  int nf, w;
+};
+
+// unpack == 0: staging <- fields; unpack != 0: fields <- staging.
+// elem_size must be 1, 2, 4 or 8.
+void launch_halo_nd(const HaloNdArgs& a, int unpack, int elem_size,
+                    hipStream_t stream);

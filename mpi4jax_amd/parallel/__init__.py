@@ -8,6 +8,8 @@ from .comm import (  # noqa: F401
     COMM_WORLD,
 )
 from .grid import CartesianGrid  # noqa: F401
+from .halo import HaloExchanger  # noqa: F401
+from . import halo  # noqa: F401
 from .ddp import average_gradients  # noqa: F401
 from .tp import (  # noqa: F401
     ColumnParallelLinear,

@@ -165,6 +165,20 @@ class CartesianGrid:
         """In-place halo exchange (internal fast path for owned buffers)."""
         return self._halo_exchange_impl(arr)
 
+    def make_halo_exchanger(self, shape, dtype, device, width=1, nfields=1,
+                            _force_remote=False):
+        """Build a reusable :class:`~.halo.HaloExchanger` for ``nfields``
+        contiguous fields of shape ``(..., ny, nx)`` (leading dims are
+        batch levels; ``ny``/``nx`` include ``width`` halo cells per side).
+
+        ``_force_remote`` is a test hook: self-peer strips travel through
+        the RCCL group as transfers to self instead of local copies.
+        """
+        from .halo import HaloExchanger
+
+        return HaloExchanger(self, shape, dtype, device, width=width,
+                             nfields=nfields, _force_remote=_force_remote)
+
     def _halo_exchange_impl(self, out):
         # imported here to avoid a circular import at package init
         from ..ops.sendrecv import sendrecv

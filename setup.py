@@ -77,7 +77,8 @@ def build_native(force=False, variant=""):
                                                f"-I{CSRC}"]
 
     objs = []
-    for src in ["kernels.hip", "shallow_water.hip", "bridge.cpp"]:
+    for src in ["kernels.hip", "shallow_water.hip", "halo.hip",
+                "bridge.cpp"]:
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
