@@ -622,8 +622,8 @@ void unpack2d(at::Tensor out, at::Tensor in) {
                   cur_stream());
 }
 
-// fused shallow-water stage launcher.  bufs order:
-// fe, fn, q, ke, h, u, v, dnh, dnu, dnv, doh, dou, dov
+// shallow-water stage launcher (stage = a SwStage id).  bufs order:
+// fe, fn, q, ke, h, u, v, dnh, dnu, dnv, doh, dou, dov, h2, u2, v2
 void sw_stage(int64_t stage, std::vector<at::Tensor> bufs, double dx,
               double dy, double dt, double nu, double cor_base,
               double cor_dj, double ab_a, double ab_b,
@@ -664,7 +664,21 @@ void sw_stage(int64_t stage, std::vector<at::Tensor> bufs, double dx,
   p.east_wall = (int)flags[4];
   p.north_wall = (int)flags[5];
   p.x_wrap = (int)flags[6];
-  launch_sw_stage((int)stage, p, is_double ? 1 : 0, cur_stream());
+  const SwStageStatus rc =
+      launch_sw_stage((int)stage, p, is_double ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc != SW_STAGE_UNKNOWN, "sw_stage: unknown stage id ", stage,
+              " (see sw_stage_ids())");
+  TORCH_CHECK(rc != SW_STAGE_F32_ONLY, "sw_stage: stage ", stage,
+              " is float32-only, got float64 buffers");
+}
+
+// name -> id of every launchable stage, straight from the SwStage enum
+py::dict sw_stage_ids() {
+  py::dict d;
+#define SW_STAGE_ITEM(name, value) d[#name] = (int)name;
+  SW_STAGE_LIST(SW_STAGE_ITEM)
+#undef SW_STAGE_ITEM
+  return d;
 }
 
 // halo helpers ------------------------------------------------------------
@@ -1138,6 +1152,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("unpack2d", &unpack2d);
   m.def("combine", &combine);
   m.def("sw_stage", &sw_stage);
+  m.def("sw_stage_ids", &sw_stage_ids);
   m.def("halo_wrap", &halo_wrap);
   m.def("pack_cols", &pack_cols);
   m.def("unpack_cols", &unpack_cols);

@@ -42,7 +42,7 @@ void launch_unpack2d(void* out, const void* in, long long rows,
                      long long cols, long long stride0, long long stride1,
                      int elem_size, hipStream_t stream);
 
-// fused shallow-water step stages (shallow_water.hip)
+// shallow-water step stages (shallow_water.hip)
 struct SwLaunchParams {
   void *fe, *fn, *q, *ke;
   void *h, *u, *v;
@@ -58,11 +58,51 @@ struct SwLaunchParams {
   int x_wrap;  // x halos are LOCAL periodic wraps (nproc_x==1), not remote
 };
 
-void launch_sw_stage(int stage, const SwLaunchParams& p, int is_double,
-                     hipStream_t stream);
+// Launchable stage ids.  The values are public: profiles/ and the docs
+// cite them, and models/shallow_water.py mirrors this table (SwStage
+// there; docs/developers.md has the id / kernel / env-knob table).  PRE =
+// derived fields fe/fn/q/ke, UPDATE = tendencies + time update, FRICTION =
+// lateral friction; V4 / V2 = 4 / 2 columns per thread (float32 only).
+#define SW_STAGE_LIST(X)                                                \
+  X(SW_PRE_SCALAR, 1)                                                   \
+  X(SW_UPDATE_SCALAR, 6)                                                \
+  X(SW_FRICTION_SCALAR, 7)                                              \
+  X(SW_UPDATE_MERGED_SCALAR, 8) /* PRE + UPDATE in one pass */          \
+  X(SW_PRE_V4, 11)                                                      \
+  X(SW_UPDATE_V4, 16)                                                   \
+  X(SW_FRICTION_V4, 17)                                                 \
+  X(SW_UPDATE_V4_MERGED, 18)                                            \
+  X(SW_UPDATE_V2, 19)                                                   \
+  X(SW_UPDATE_V2_NT, 20) /* + nontemporal streaming hints */            \
+  X(SW_UPDATE_V2_TILE4, 21) /* band-tiled blocks: 4 / 8 / 16 rows */    \
+  X(SW_UPDATE_V2_TILE8, 22)                                             \
+  X(SW_UPDATE_V2_TILE16, 23)                                            \
+  X(SW_FRICTION_V2, 27)                                                 \
+  X(SW_FRICTION_V2_INTERIOR, 28) /* halo-independent pairs (overlap) */ \
+  X(SW_FRICTION_V2_RING, 29)     /* the rest of SW_FRICTION_V2 */       \
+  X(SW_STEP1, 30) /* whole world-1 step, one launch */                  \
+  X(SW_STEP1_512, 31)                                                   \
+  X(SW_FUSED_FAST_RINGA, 32) /* LDS-fused update+friction + ring A */   \
+  X(SW_FUSED_RINGB, 33)      /* ring friction from the u'/v' strip */   \
+  X(SW_FUSED_RING3, 34)      /* 32 + 33 back to back (world 1) */
 
-// halo-exchange helpers (shallow_water.hip): periodic wrap and multi-field
-// column pack/unpack (up to 3 fields)
+enum SwStage : int {
+#define SW_STAGE_ENUM(name, value) name = value,
+  SW_STAGE_LIST(SW_STAGE_ENUM)
+#undef SW_STAGE_ENUM
+};
+
+enum SwStageStatus : int {
+  SW_STAGE_OK = 0,
+  SW_STAGE_UNKNOWN = 1,   // not a SwStage id: nothing launched
+  SW_STAGE_F32_ONLY = 2,  // float-only stage with f64 buffers: ditto
+};
+
+SwStageStatus launch_sw_stage(int stage, const SwLaunchParams& p,
+                              int is_double, hipStream_t stream);
+
+// shallow-water model halo-exchange helpers (halo.hip): periodic wrap and
+// multi-field column pack/unpack (up to 3 fields)
 void launch_halo_wrap(void* const* fields, int nf, long long ny,
                       long long nx, int side, int is_double,
                       hipStream_t stream);
@@ -73,7 +113,7 @@ void launch_unpack_cols(void* const* fields, const void* buf, int nf,
                         long long ny, long long nx, long long col,
                         int is_double, hipStream_t stream);
 
-// corner pack/unpack for the single-group halo exchange
+// corner pack/unpack for the single-group halo exchange (halo.hip)
 void launch_pack_corners(void* buf, void* const* fields, int nf,
                          long long ny, long long nx, int is_double,
                          hipStream_t stream);
@@ -81,8 +121,9 @@ void launch_unpack_corners(void* const* fields, const void* buf, int nf,
                            long long ny, long long nx, int mask,
                            int is_double, hipStream_t stream);
 
-// merged halo staging: one launch covering the periodic wrap, both column
-// packs and the corner pack (resp. the column + corner unpacks) — the
+// merged halo staging (halo.hip): one launch covering the periodic wrap,
+// both column packs and the corner pack (resp. the column + corner
+// unpacks) — the
 // per-exchange launch count is what bounds strong scaling once the local
 // domain is small.  Null buffer => that segment is skipped; wrap_side -1
 // => no wrap.  The unpack skips a column's j=0 / j=ny-1 cell when the

@@ -1,20 +1,32 @@
-// Fused CDNA4 kernels for the shallow-water step (gfx950).
+// Shallow-water stencil kernels for CDNA4 (gfx950).  Stencil code only:
+// the model's halo staging kernels live in halo.hip.
 //
-// The eager torch path runs ~300 small kernels per model step (measured,
-// profiles/); these five fused stencil kernels + the h/u/v halo exchange
-// are the whole step.  Key idea: the derived fields (fe/fn/q/ke and the
-// friction gradients) never need a halo *exchange* — at an open edge their
-// halo value equals the same formula evaluated on local data (h/u/v halos
-// are fresh), bitwise-identical to what the neighbor would send; at a
-// closed edge the eager path leaves zeros.  So each kernel computes
-// interior + readable halos with an open/closed mask and the only
-// communication left is the h/u/v ring exchange.
+// Key idea: the derived fields (fe/fn/q/ke and the friction gradients)
+// never need a halo *exchange* — at an open edge their halo value equals
+// the same formula evaluated on local data (h/u/v halos are fresh),
+// bitwise-identical to what the neighbor would send; at a closed edge the
+// eager path leaves zeros.  So each kernel computes interior + readable
+// halos with an open/closed mask and the only communication left is the
+// h/u/v ring exchange.  Indices are 32-bit (int64 div/mod per element
+// measured 2-4x off the HBM roofline).
 //
-// Mapping: one cell per thread, blockIdx.x*256 covering columns (so a
-// wave64's lanes touch consecutive columns -> fully coalesced), blockIdx.y
-// covering rows; the benchmark grid launches ~27k workgroups, far above
-// the 256-CU residency needed to fill all 8 XCDs.  Indices are 32-bit
-// (int64 div/mod per element measured 2-4x off the HBM roofline).
+// Four layers, each built on the one before; launch_sw_stage at the end
+// of the file maps every SwStage id (kernels.h) to its kernel(s), and
+// docs/developers.md has the id / kernel / env-knob table.
+//   1. Scalar reference stages (f32 + f64): one cell per thread.
+//      stage{6,7,8}_cell are the single definition of their formulas and
+//      boundary masks (sw_stage{6,7,8}_kernel only map a block to cells);
+//      stage 1 keeps a kernel body and a float cell body, see stage1_cell.
+//   2. Vector pipeline (f32): 4 columns per thread (sw_stage1v/6v/7v/18v)
+//      or 2 (sw_stage19t/21t, sw_stage27v/28v/29v).  A pack inside the
+//      SW_FAST_BOUNDS region runs mask-free vector math; any other pack
+//      calls the scalar cell bodies.
+//   3. Fused ring form (f32): sw_stage30t keeps the post-update u'/v' in
+//      LDS and applies the friction from there; sw_stage30_ringA/ringB
+//      cover the boundary ring through the fe/fn strip (multi-rank: a real
+//      strip exchange runs between them).
+//   4. Single-launch step (f32, world size 1): sw_step1t, the fused form
+//      with the ring folded into perimeter tiles.
 
 #include <hip/hip_runtime.h>
 
@@ -25,18 +37,23 @@ namespace {
 constexpr int kBlock = 256;
 
 // XCD-aware block mapping: the dispatcher places block b on XCD b%8, so a
-// plain (col-chunk, row) 2-D grid scatters adjacent rows across XCDs and
-// every j±1 stencil read misses that XCD's L2.  The bijective remap below
-// gives each XCD a contiguous band of row-major tiles, so neighbor rows
-// are L2-resident (MI355X_MICROARCH.md §Workgroup dispatch; speed-only).
+// plain row-major grid scatters adjacent rows across XCDs and every j±1
+// stencil read misses that XCD's L2.  This bijective remap of block b of
+// T gives each XCD a contiguous band of ids, so neighbor rows are
+// L2-resident (MI355X_MICROARCH.md §Workgroup dispatch; speed-only).
+// (B = unsigned where the caller has b >= 0 from a branch: shift, no fix-up)
+template <typename B>
+__host__ __device__ inline int xcd_band_id(B b, int T) {
+  const int q8_ = T / 8, r8_ = T % 8, xc_ = b % 8, yc_ = b / 8;
+  return (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
+         + yc_;
+}
+
+// one cell per thread: block -> (row j, 256-column chunk), so a wave64's
+// lanes touch consecutive columns (fully coalesced)
 #define SW_BLOCK_MAP(ny, nx)                                               \
   const int gx_ = (nx + kBlock - 1) / kBlock;                              \
-  const int T_ = (int)gridDim.x;                                           \
-  const int t_ = (int)blockIdx.x;                                          \
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = t_ % 8, yc_ = t_ / 8;        \
-  const int id_ =                                                          \
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)  \
-      + yc_;                                                               \
+  const int id_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);            \
   const int j = id_ / gx_;                                                 \
   const int i = (id_ % gx_) * kBlock + (int)threadIdx.x
 
@@ -79,6 +96,18 @@ struct SwArgs {
   T ab_a, ab_b;        // Adams-Bashforth coefficients (b=0 -> Euler)
   SwFlags f;
 };
+
+// The fast region: cells [jmin, jmax] x [imin, imax) whose whole stencil
+// is mask-free (open halos readable, no wall row/column, no hc clamp), so
+// the vector kernels run the plain formulas there; each adds its own
+// pack-width terms to the test.  Declares the four bounds as locals (a
+// macro like SW_BLOCK_MAP, not a struct: every struct or function form
+// tried changed the register allocation of the vector kernels).
+#define SW_FAST_BOUNDS(ny, nx, f)                                          \
+  const int jmin = (f).south_open ? 1 : 2;                                 \
+  const int jmax = ((f).north_open && !(f).north_wall) ? ny - 2 : ny - 3;  \
+  const int imin = (f).west_open ? 1 : 2;                                  \
+  const int imax = ((f).east_open && !(f).east_wall) ? nx - 1 : nx - 2
 
 // hc = h padded by edge replication at closed halos (reference
 // shallow_water.py:278-279 + enforce_boundaries); at open halos hc == h.
@@ -316,46 +345,52 @@ __global__ void sw_stage8_kernel(SwArgs<T> a) {
 // tendencies + AB/Euler update written to h2/u2/v2 — no in-place hazard,
 // one full pass of traffic saved.
 template <typename T>
+__device__ inline void stage6_cell(const SwArgs<T>& a, int j, int i) {
+  const int ny = (int)a.ny, nx = (int)a.nx;
+  const int idx = j * nx + i;
+  T h_ = a.h[idx], u_ = a.u[idx], v_ = a.v[idx];
+  if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
+    // halo cells: fields pass through (exchange updates them next),
+    // tendencies stay zero
+    a.h2[idx] = h_;
+    a.u2[idx] = u_;
+    a.v2[idx] = v_;
+    return;
+  }
+
+  T dnh = -(a.fe[idx] - a.fe[idx - 1]) / a.dx -
+          (a.fn[idx] - a.fn[idx - nx]) / a.dy;
+  a.dnh[idx] = dnh;
+
+  T dnu = -G * (a.h[idx + 1] - h_) / a.dx +
+          T(0.5) * (a.q[idx] * T(0.5) * (a.fn[idx] + a.fn[idx + 1]) +
+                    a.q[idx - nx] * T(0.5) *
+                        (a.fn[idx - nx] + a.fn[idx - nx + 1]));
+  dnu -= (a.ke[idx + 1] - a.ke[idx]) / a.dx;
+  a.dnu[idx] = dnu;
+
+  T dnv = -G * (a.h[idx + nx] - h_) / a.dy -
+          T(0.5) * (a.q[idx] * T(0.5) * (a.fe[idx] + a.fe[idx + nx]) +
+                    a.q[idx - 1] * T(0.5) *
+                        (a.fe[idx - 1] + a.fe[idx + nx - 1]));
+  dnv -= (a.ke[idx + nx] - a.ke[idx]) / a.dy;
+  a.dnv[idx] = dnv;
+
+  T uu = u_ + a.dt * (a.ab_a * dnu + a.ab_b * a.dou[idx]);
+  T vv = v_ + a.dt * (a.ab_a * dnv + a.ab_b * a.dov[idx]);
+  a.h2[idx] = h_ + a.dt * (a.ab_a * dnh + a.ab_b * a.doh[idx]);
+  if (a.f.east_wall && i == nx - 2) uu = T(0);
+  if (a.f.north_wall && j == ny - 2) vv = T(0);
+  a.u2[idx] = uu;
+  a.v2[idx] = vv;
+}
+
+template <typename T>
 __global__ void sw_stage6_kernel(SwArgs<T> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   SW_BLOCK_MAP(ny, nx);
   if (i < nx && j < ny) {
-    const int idx = j * nx + i;
-    T h_ = a.h[idx], u_ = a.u[idx], v_ = a.v[idx];
-    if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
-      // halo cells: fields pass through (exchange updates them next),
-      // tendencies stay zero
-      a.h2[idx] = h_;
-      a.u2[idx] = u_;
-      a.v2[idx] = v_;
-      return;
-    }
-
-    T dnh = -(a.fe[idx] - a.fe[idx - 1]) / a.dx -
-            (a.fn[idx] - a.fn[idx - nx]) / a.dy;
-    a.dnh[idx] = dnh;
-
-    T dnu = -G * (a.h[idx + 1] - h_) / a.dx +
-            T(0.5) * (a.q[idx] * T(0.5) * (a.fn[idx] + a.fn[idx + 1]) +
-                      a.q[idx - nx] * T(0.5) *
-                          (a.fn[idx - nx] + a.fn[idx - nx + 1]));
-    dnu -= (a.ke[idx + 1] - a.ke[idx]) / a.dx;
-    a.dnu[idx] = dnu;
-
-    T dnv = -G * (a.h[idx + nx] - h_) / a.dy -
-            T(0.5) * (a.q[idx] * T(0.5) * (a.fe[idx] + a.fe[idx + nx]) +
-                      a.q[idx - 1] * T(0.5) *
-                          (a.fe[idx - 1] + a.fe[idx + nx - 1]));
-    dnv -= (a.ke[idx + nx] - a.ke[idx]) / a.dy;
-    a.dnv[idx] = dnv;
-
-    T uu = u_ + a.dt * (a.ab_a * dnu + a.ab_b * a.dou[idx]);
-    T vv = v_ + a.dt * (a.ab_a * dnv + a.ab_b * a.dov[idx]);
-    a.h2[idx] = h_ + a.dt * (a.ab_a * dnh + a.ab_b * a.doh[idx]);
-    if (a.f.east_wall && i == nx - 2) uu = T(0);
-    if (a.f.north_wall && j == ny - 2) vv = T(0);
-    a.u2[idx] = uu;
-    a.v2[idx] = vv;
+    stage6_cell(a, j, i);
   }
 }
 
@@ -363,27 +398,33 @@ __global__ void sw_stage6_kernel(SwArgs<T> a) {
 // (each g-gradient evaluated twice — FP is free, the array pass is not),
 // updated u/v written to u2/v2.
 template <typename T>
+__device__ inline void stage7_cell(const SwArgs<T>& a, int j, int i) {
+  const int ny = (int)a.ny, nx = (int)a.nx;
+  const int idx = j * nx + i;
+  T u_ = a.u[idx], v_ = a.v[idx];
+  if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
+    a.u2[idx] = u_;
+    a.v2[idx] = v_;
+    return;
+  }
+  T lu = (gu_of_u(a, j, i) - gu_of_u(a, j, i - 1)) / a.dx +
+         (gv_of_u(a, j, i) - gv_of_u(a, j - 1, i)) / a.dy;
+  T lv = (gu_of_v(a, j, i) - gu_of_v(a, j, i - 1)) / a.dx +
+         (gv_of_v(a, j, i) - gv_of_v(a, j - 1, i)) / a.dy;
+  T uu = u_ + a.dt * lu;
+  T vv = v_ + a.dt * lv;
+  if (a.f.east_wall && i == nx - 2) uu = T(0);
+  if (a.f.north_wall && j == ny - 2) vv = T(0);
+  a.u2[idx] = uu;
+  a.v2[idx] = vv;
+}
+
+template <typename T>
 __global__ void sw_stage7_kernel(SwArgs<T> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   SW_BLOCK_MAP(ny, nx);
   if (i < nx && j < ny) {
-    const int idx = j * nx + i;
-    T u_ = a.u[idx], v_ = a.v[idx];
-    if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
-      a.u2[idx] = u_;
-      a.v2[idx] = v_;
-      return;
-    }
-    T lu = (gu_of_u(a, j, i) - gu_of_u(a, j, i - 1)) / a.dx +
-           (gv_of_u(a, j, i) - gv_of_u(a, j - 1, i)) / a.dy;
-    T lv = (gu_of_v(a, j, i) - gu_of_v(a, j, i - 1)) / a.dx +
-           (gv_of_v(a, j, i) - gv_of_v(a, j - 1, i)) / a.dy;
-    T uu = u_ + a.dt * lu;
-    T vv = v_ + a.dt * lv;
-    if (a.f.east_wall && i == nx - 2) uu = T(0);
-    if (a.f.north_wall && j == ny - 2) vv = T(0);
-    a.u2[idx] = uu;
-    a.v2[idx] = vv;
+    stage7_cell(a, j, i);
   }
 }
 
@@ -447,7 +488,10 @@ __device__ inline vf2 rcp2(vf2 x) {
 }
 
 
-// scalar per-cell bodies (shared by scalar kernels' fallback)
+// stage 1 body for the vector kernel's edge packs.  Same text as
+// sw_stage1_kernel<float>'s; kept apart because calling one function from
+// both changes the scalar kernel's generated code (register count
+// included), which a refactor of this file must not do.
 __device__ inline void stage1_cell(const SwArgs<float>& a, int j, int i) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int idx = j * nx + i;
@@ -485,81 +529,18 @@ __device__ inline void stage1_cell(const SwArgs<float>& a, int j, int i) {
   a.ke[idx] = ke;
 }
 
-__device__ inline void stage6_cell(const SwArgs<float>& a, int j, int i) {
-  const int ny = (int)a.ny, nx = (int)a.nx;
-  const int idx = j * nx + i;
-  float h_ = a.h[idx], u_ = a.u[idx], v_ = a.v[idx];
-  if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
-    a.h2[idx] = h_;
-    a.u2[idx] = u_;
-    a.v2[idx] = v_;
-    return;
-  }
-  float dnh = -(a.fe[idx] - a.fe[idx - 1]) / a.dx -
-              (a.fn[idx] - a.fn[idx - nx]) / a.dy;
-  a.dnh[idx] = dnh;
-  float dnu = -G * (a.h[idx + 1] - h_) / a.dx +
-              0.5f * (a.q[idx] * 0.5f * (a.fn[idx] + a.fn[idx + 1]) +
-                      a.q[idx - nx] * 0.5f *
-                          (a.fn[idx - nx] + a.fn[idx - nx + 1]));
-  dnu -= (a.ke[idx + 1] - a.ke[idx]) / a.dx;
-  a.dnu[idx] = dnu;
-  float dnv = -G * (a.h[idx + nx] - h_) / a.dy -
-              0.5f * (a.q[idx] * 0.5f * (a.fe[idx] + a.fe[idx + nx]) +
-                      a.q[idx - 1] * 0.5f *
-                          (a.fe[idx - 1] + a.fe[idx + nx - 1]));
-  dnv -= (a.ke[idx + nx] - a.ke[idx]) / a.dy;
-  a.dnv[idx] = dnv;
-  float uu = u_ + a.dt * (a.ab_a * dnu + a.ab_b * a.dou[idx]);
-  float vv = v_ + a.dt * (a.ab_a * dnv + a.ab_b * a.dov[idx]);
-  a.h2[idx] = h_ + a.dt * (a.ab_a * dnh + a.ab_b * a.doh[idx]);
-  if (a.f.east_wall && i == nx - 2) uu = 0.f;
-  if (a.f.north_wall && j == ny - 2) vv = 0.f;
-  a.u2[idx] = uu;
-  a.v2[idx] = vv;
-}
-
-__device__ inline void stage7_cell(const SwArgs<float>& a, int j, int i) {
-  const int ny = (int)a.ny, nx = (int)a.nx;
-  const int idx = j * nx + i;
-  float u_ = a.u[idx], v_ = a.v[idx];
-  if (j < 1 || j > ny - 2 || i < 1 || i > nx - 2) {
-    a.u2[idx] = u_;
-    a.v2[idx] = v_;
-    return;
-  }
-  float lu = (gu_of_u(a, j, i) - gu_of_u(a, j, i - 1)) / a.dx +
-             (gv_of_u(a, j, i) - gv_of_u(a, j - 1, i)) / a.dy;
-  float lv = (gu_of_v(a, j, i) - gu_of_v(a, j, i - 1)) / a.dx +
-             (gv_of_v(a, j, i) - gv_of_v(a, j - 1, i)) / a.dy;
-  float uu = u_ + a.dt * lu;
-  float vv = v_ + a.dt * lv;
-  if (a.f.east_wall && i == nx - 2) uu = 0.f;
-  if (a.f.north_wall && j == ny - 2) vv = 0.f;
-  a.u2[idx] = uu;
-  a.v2[idx] = vv;
-}
-
 // simpler pack mapping: thread t covers row j = t / packs_per_row,
 // columns [4*(t % ppr), 4*(t % ppr)+3]
 __global__ void sw_stage1v(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 3) / 4;
-  // XCD-aware block remap (same rationale as SW_BLOCK_MAP): give each XCD
-  // a contiguous band of rows so j±1 stencil rows hit that XCD's L2
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   const int j = t / ppr;
   const int i0 = (t % ppr) * 4;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
-  const int imin = a.f.west_open ? 0 + 1 : 2;  // cols use i-1 only in ke
+  SW_FAST_BOUNDS(ny, nx, a.f);
+  // j >= 1, not jmin: no row j-1 input of this stage is masked
   const bool fast = j >= 1 && j <= jmax && i0 >= imin && i0 + 4 <= imax &&
                     a.f.west_open && a.f.east_open;
   if (!fast) {
@@ -585,18 +566,13 @@ __global__ void sw_stage1v(SwArgs<float> a) {
 __global__ void sw_stage6v(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 3) / 4;
-  // XCD-aware block remap (same rationale as SW_BLOCK_MAP): give each XCD
-  // a contiguous band of rows so j±1 stencil rows hit that XCD's L2
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   const int j = t / ppr;
   const int i0 = (t % ppr) * 4;
+  // own rule, not SW_FAST_BOUNDS: the inputs are stage 1's already-masked
+  // arrays, so only the interior test and the two wall rows/columns matter
   const int jmax = a.f.north_wall ? ny - 3 : ny - 2;
   const int imax = a.f.east_wall ? nx - 2 : nx - 1;
   const bool fast = j >= 1 && j <= jmax && i0 >= 1 && i0 + 4 <= imax;
@@ -636,22 +612,12 @@ __global__ void sw_stage6v(SwArgs<float> a) {
 __global__ void sw_stage7v(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 3) / 4;
-  // XCD-aware block remap (same rationale as SW_BLOCK_MAP): give each XCD
-  // a contiguous band of rows so j±1 stencil rows hit that XCD's L2
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   const int j = t / ppr;
   const int i0 = (t % ppr) * 4;
-  const int jmin = a.f.south_open ? 1 : 2;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = a.f.west_open ? 1 : 2;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, a.f);
   const bool fast = j >= jmin && j <= jmax && i0 >= imin &&
                     i0 + 4 <= imax && i0 + 5 <= nx;
   if (!fast) {
@@ -685,22 +651,12 @@ __global__ void sw_stage7v(SwArgs<float> a) {
 __global__ void sw_stage18v(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 3) / 4;
-  // XCD-aware block remap (same rationale as SW_BLOCK_MAP): give each XCD
-  // a contiguous band of rows so j±1 stencil rows hit that XCD's L2
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   const int j = t / ppr;
   const int i0 = (t % ppr) * 4;
-  const int jmin = a.f.south_open ? 1 : 2;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = a.f.west_open ? 1 : 2;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, a.f);
   const bool fast = j >= jmin && j <= jmax && i0 >= imin && i0 + 4 <= imax;
   if (!fast) {
     for (int c = 0; c < 4 && i0 + c < nx; ++c) stage8_cell(a, j, i0 + c);
@@ -787,15 +743,30 @@ __global__ void sw_stage18v(SwArgs<float> a) {
   st4(a.v2, idx, V00 + a.dt * (a.ab_a * dnv + a.ab_b * dov));
 }
 
+// the friction update of one 2-column pack from its ten neighbour packs
+// (u and v; west, centre, east, north, south), rdx form — the single
+// definition behind stage 27/28/29 and the LDS friction pass
+struct UV2 {
+  vf2 u, v;
+};
+
+__device__ inline UV2 friction_pair(const SwArgs<float>& a, vf2 uw, vf2 uc,
+                                    vf2 ue, vf2 un, vf2 us, vf2 vw, vf2 vcc,
+                                    vf2 ve, vf2 vn, vf2 vs) {
+  const float nu = a.nu;
+  vf2 lu = (nu * (ue - uc) * a.rdx - nu * (uc - uw) * a.rdx) * a.rdx +
+           (nu * (un - uc) * a.rdy - nu * (uc - us) * a.rdy) * a.rdy;
+  vf2 lv = (nu * (ve - vcc) * a.rdx - nu * (vcc - vw) * a.rdx) * a.rdx +
+           (nu * (vn - vcc) * a.rdy - nu * (vcc - vs) * a.rdy) * a.rdy;
+  return {uc + a.dt * lu, vcc + a.dt * lv};
+}
+
 // stage 27 = stage 17 (friction Laplacian) at 2 columns/thread — same
 // occupancy rationale as stage 19 below.
 __device__ inline void stage27_pair(const SwArgs<float>& a, int j,
                                     int i0) {
   const int ny = (int)a.ny, nx = (int)a.nx;
-  const int jmin = a.f.south_open ? 1 : 2;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = a.f.west_open ? 1 : 2;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, a.f);
   const bool fast = j >= jmin && j <= jmax && i0 >= imin &&
                     i0 + 2 <= imax && i0 + 2 < nx;
   if (!fast) {
@@ -807,26 +778,16 @@ __device__ inline void stage27_pair(const SwArgs<float>& a, int j,
   vf2 un = ld2(a.u, idx + nx), us = ld2(a.u, idx - nx);
   vf4 V0A = ld4(a.v, idx - 1);
   vf2 vn = ld2(a.v, idx + nx), vs = ld2(a.v, idx - nx);
-  vf2 uw = x01(U0A), uc = x12(U0A), ue = x23(U0A);
-  vf2 vw = x01(V0A), vcc = x12(V0A), ve = x23(V0A);
-  const float nu = a.nu;
-  vf2 lu = (nu * (ue - uc) * a.rdx - nu * (uc - uw) * a.rdx) * a.rdx +
-           (nu * (un - uc) * a.rdy - nu * (uc - us) * a.rdy) * a.rdy;
-  vf2 lv = (nu * (ve - vcc) * a.rdx - nu * (vcc - vw) * a.rdx) * a.rdx +
-           (nu * (vn - vcc) * a.rdy - nu * (vcc - vs) * a.rdy) * a.rdy;
-  st2(a.u2, idx, uc + a.dt * lu);
-  st2(a.v2, idx, vcc + a.dt * lv);
+  const UV2 r = friction_pair(a, x01(U0A), x12(U0A), x23(U0A), un, us,
+                              x01(V0A), x12(V0A), x23(V0A), vn, vs);
+  st2(a.u2, idx, r.u);
+  st2(a.v2, idx, r.v);
 }
 
 __global__ void sw_stage27v(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 1) / 2;
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   stage27_pair(a, t / ppr, (t % ppr) * 2);
@@ -847,12 +808,7 @@ __device__ inline bool stage27_pair_independent(const SwArgs<float>& a,
 __global__ void sw_stage28v(SwArgs<float> a) {  // interior pairs only
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 1) / 2;
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   const int j = t / ppr, i0 = (t % ppr) * 2;
@@ -923,10 +879,7 @@ __device__ inline void st2s(float* p, long long off, vf2 v) {
 __host__ __device__ inline bool stage19_pair_fast(const SwArgs<float>& a, int j,
                                          int i0) {
   const int ny = (int)a.ny, nx = (int)a.nx;
-  const int jmin = a.f.south_open ? 1 : 2;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = a.f.west_open ? 1 : 2;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, a.f);
   return j >= jmin && j <= jmax && i0 >= imin && i0 + 2 <= imax &&
          i0 + 3 < nx;
 }
@@ -1034,12 +987,7 @@ template <bool NT>
 __global__ void sw_stage19t(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int ppr = (nx + 1) / 2;
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int t = bid_ * (int)blockDim.x + (int)threadIdx.x;
   if (t >= ppr * ny) return;
   stage19_cells<NT>(a, t / ppr, (t % ppr) * 2);
@@ -1058,12 +1006,7 @@ __global__ void sw_stage21t(SwArgs<float> a) {
   const int ppr = (nx + 1) / 2;
   constexpr int TPC = 256 / TJ;  // thread-pairs (2 cols each) per tile row
   const int nti = (ppr + TPC - 1) / TPC;
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int tj = bid_ / nti, ti = bid_ % nti;
   const int jj = (int)threadIdx.x / TPC, ii = (int)threadIdx.x % TPC;
   const int j = tj * TJ + jj;
@@ -1103,6 +1046,18 @@ __device__ inline bool s30_in_ring(const SwArgs<float>& a, int jj,
   return jj <= 3 || jj >= ny - 4 || i0 <= 5 || i0 >= nx - 7;
 }
 
+// the column a local periodic wrap copies into column i: the opposite
+// interior edge for the two x halos under x_wrap, else i itself
+__device__ inline int x_wrap_src(const SwArgs<float>& a, int i) {
+  const int nx = (int)a.nx;
+  int is = i;
+  if (a.f.x_wrap) {
+    if (i == 0) is = nx - 2;
+    else if (i == nx - 1) is = 1;
+  }
+  return is;
+}
+
 // what the ring friction reads at (jj, ii): the mid-step exchange's
 // value.  Local periodic x halos (x_wrap) map to their wrap source;
 // remote open halos read the EXCHANGED fe/fn strip (the N>1 fused step
@@ -1112,11 +1067,7 @@ __device__ inline bool s30_in_ring(const SwArgs<float>& a, int jj,
 __device__ inline void s30_read_uv(const SwArgs<float>& a, int jj, int ii,
                                    float* uu, float* vv) {
   const int ny = (int)a.ny, nx = (int)a.nx;
-  int is = ii;
-  if (a.f.x_wrap) {
-    if (ii == 0) is = nx - 2;
-    else if (ii == nx - 1) is = 1;
-  }
+  const int is = x_wrap_src(a, ii);
   const long long idx = (long long)jj * nx + is;
   const bool closed = (jj == 0 && !a.f.south_open) ||
                       (jj == ny - 1 && !a.f.north_open) ||
@@ -1151,29 +1102,39 @@ constexpr int kFill30 = kTR30 * kTP30;     // LDS fill tasks
 __host__ __device__ inline bool s30_fast_out(const SwArgs<float>& a, int j,
                                     int i0) {
   const int ny = (int)a.ny, nx = (int)a.nx;
-  const int jmin = a.f.south_open ? 1 : 2;
-  const int jmax = (a.f.north_open && !a.f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = a.f.west_open ? 1 : 2;
-  const int imax = (a.f.east_open && !a.f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, a.f);
   return j - 1 >= jmin && j + 1 <= jmax && i0 - 2 >= imin &&
          i0 + 4 <= imax && i0 + 5 < nx;
+}
+
+typedef float S30Tile[kTR30][2 * kTP30];
+
+// friction of the output pair at LDS tile row lr, column x, from the
+// post-update u'/v' tile
+__device__ inline UV2 s30_friction_lds(const SwArgs<float>& a,
+                                       const S30Tile& su, const S30Tile& sv,
+                                       int lr, int x) {
+  return friction_pair(
+      a, (vf2){su[lr][x - 1], su[lr][x]}, (vf2){su[lr][x], su[lr][x + 1]},
+      (vf2){su[lr][x + 1], su[lr][x + 2]},
+      (vf2){su[lr + 1][x], su[lr + 1][x + 1]},
+      (vf2){su[lr - 1][x], su[lr - 1][x + 1]},
+      (vf2){sv[lr][x - 1], sv[lr][x]}, (vf2){sv[lr][x], sv[lr][x + 1]},
+      (vf2){sv[lr][x + 1], sv[lr][x + 2]},
+      (vf2){sv[lr + 1][x], sv[lr + 1][x + 1]},
+      (vf2){sv[lr - 1][x], sv[lr - 1][x + 1]});
 }
 
 template <int NT_>
 __global__ void __launch_bounds__(NT_) sw_stage30t(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
   const int bpc = (nx + 2 * kPC30 - 1) / (2 * kPC30);  // blocks per band
-  const int T_ = (int)gridDim.x;
-  const int b_ = (int)blockIdx.x;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = b_ % 8, yc_ = b_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((int)blockIdx.x, (int)gridDim.x);
   const int jb = (bid_ / bpc) * kTJ30;       // first owned output row
   const int cb = (bid_ % bpc) * 2 * kPC30;   // first owned output column
   const int tid = (int)threadIdx.x;
 
-  __shared__ float su[kTR30][2 * kTP30], sv[kTR30][2 * kTP30];
+  __shared__ S30Tile su, sv;
   for (int t = tid; t < kFill30; t += NT_) {
     const int lr = t / kTP30, lp = t % kTP30;
     const int rr = jb - 1 + lr;
@@ -1203,24 +1164,10 @@ __global__ void __launch_bounds__(NT_) sw_stage30t(SwArgs<float> a) {
     const int j = jb + ro;
     const int i0 = cb + 2 * po;
     if (!s30_fast_out(a, j, i0)) continue;  // ring kernels own this pair
-    const int lr = ro + 1, x = 2 * po + 2;
     const long long idx = (long long)j * nx + i0;
-    // stage27_pair math, inputs from LDS
-    vf2 uw = {su[lr][x - 1], su[lr][x]}, uc = {su[lr][x], su[lr][x + 1]},
-        ue = {su[lr][x + 1], su[lr][x + 2]};
-    vf2 un = {su[lr + 1][x], su[lr + 1][x + 1]},
-        us = {su[lr - 1][x], su[lr - 1][x + 1]};
-    vf2 vw = {sv[lr][x - 1], sv[lr][x]}, vcc = {sv[lr][x], sv[lr][x + 1]},
-        ve = {sv[lr][x + 1], sv[lr][x + 2]};
-    vf2 vn = {sv[lr + 1][x], sv[lr + 1][x + 1]},
-        vs = {sv[lr - 1][x], sv[lr - 1][x + 1]};
-    const float nu = a.nu;
-    vf2 lu = (nu * (ue - uc) * a.rdx - nu * (uc - uw) * a.rdx) * a.rdx +
-             (nu * (un - uc) * a.rdy - nu * (uc - us) * a.rdy) * a.rdy;
-    vf2 lv = (nu * (ve - vcc) * a.rdx - nu * (vcc - vw) * a.rdx) * a.rdx +
-             (nu * (vn - vcc) * a.rdy - nu * (vcc - vs) * a.rdy) * a.rdy;
-    st2(a.u2, idx, uc + a.dt * lu);
-    st2(a.v2, idx, vcc + a.dt * lv);
+    const UV2 r = s30_friction_lds(a, su, sv, ro + 1, 2 * po + 2);
+    st2(a.u2, idx, r.u);
+    st2(a.v2, idx, r.v);
   }
 }
 
@@ -1326,11 +1273,7 @@ __global__ void sw_stage30_ringB(SwArgs<float> a) {
     // the real end-of-step exchange overwrites them.  Closed halos:
     // pass-through is the final value.  A wrap source that is itself a
     // (closed-y) halo cell passes the pre-update field through.
-    int is = i;
-    if (a.f.x_wrap) {
-      if (i == 0) is = nx - 2;
-      else if (i == nx - 1) is = 1;
-    }
+    const int is = x_wrap_src(a, i);
     const long long sdx = (long long)j * nx + is;
     if (is == i || j < 1 || j > ny - 2) {
       a.h2[idx] = a.h[sdx];  // pass-through (possibly x-wrapped corner)
@@ -1387,10 +1330,7 @@ __host__ __device__ inline int s1_floordiv(int x, int d) {
 
 __host__ __device__ inline S1Tiles s1_tiles(int ny, int nx,
                                             const SwFlags& f) {
-  const int jmin = f.south_open ? 1 : 2;
-  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = f.west_open ? 1 : 2;
-  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, f);
   S1Tiles t;
   t.bpc = (nx + 2 * kPC30 - 1) / (2 * kPC30);
   t.bands = (ny + kTJ30 - 1) / kTJ30;
@@ -1442,12 +1382,7 @@ __host__ __device__ inline int s1_block_tile(const S1Tiles& tl, int b,
     }
     return 1;
   }
-  const int T_ = tl.nfast;
-  const int f_ = b - tl.nper_pad;
-  const int q8_ = T_ / 8, r8_ = T_ % 8, xc_ = f_ % 8, yc_ = f_ / 8;
-  const int bid_ =
-      (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-      + yc_;
+  const int bid_ = xcd_band_id((unsigned)(b - tl.nper_pad), tl.nfast);
   const int fw = tl.tc1 - tl.tc0 + 1;
   *tr = tl.tr0 + bid_ / fw;
   *tc = tl.tc0 + bid_ % fw;
@@ -1475,10 +1410,7 @@ __host__ __device__ inline S1Rect s1_clip_rect(int r0, int r1, int p0,
 __host__ __device__ inline S1Rect s1_fill_rect(int ny, int nx,
                                                const SwFlags& f, int jb,
                                                int cb) {
-  const int jmin = f.south_open ? 1 : 2;
-  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = f.west_open ? 1 : 2;
-  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, f);
   const int ihi = imax - 2 < nx - 4 ? imax - 2 : nx - 4;
   return s1_clip_rect(jmin - (jb - 1), jmax - (jb - 1),
                       s1_floordiv(imin - (cb - 2) + 1, 2),
@@ -1489,10 +1421,7 @@ __host__ __device__ inline S1Rect s1_fill_rect(int ny, int nx,
 __host__ __device__ inline S1Rect s1_out_rect(int ny, int nx,
                                               const SwFlags& f, int jb,
                                               int cb) {
-  const int jmin = f.south_open ? 1 : 2;
-  const int jmax = (f.north_open && !f.north_wall) ? ny - 2 : ny - 3;
-  const int imin = f.west_open ? 1 : 2;
-  const int imax = (f.east_open && !f.east_wall) ? nx - 1 : nx - 2;
+  SW_FAST_BOUNDS(ny, nx, f);
   const int ohi = imax - 4 < nx - 6 ? imax - 4 : nx - 6;
   return s1_clip_rect(jmin + 1 - jb, jmax - 1 - jb,
                       s1_floordiv(imin + 2 - cb + 1, 2),
@@ -1547,9 +1476,11 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
   const int cb = tc * 2 * kPC30;   // first owned output column
   const int tid = (int)threadIdx.x;
 
-  __shared__ float su[kTR30][2 * kTP30], sv[kTR30][2 * kTP30];
+  __shared__ S30Tile su, sv;
 
   // pass 1, vector: the stage-19 update of every fast pair of the tile
+  // (sw_stage30t's fill loop minus the fe/fn strip stores; sharing one
+  // function changed both kernels' integer code, so the copy stays)
   for (int t = tid; t < kFill30; t += NT_) {
     const int lr = t / kTP30, lp = t % kTP30;
     const int rr = jb - 1 + lr;
@@ -1584,11 +1515,7 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
       if (rr < 0 || rr >= ny || ii < 0 || ii >= nx) continue;
       if (stage19_pair_fast(a, rr, ii & ~1)) continue;  // vector pass did it
       // the cell whose u'/v' this entry holds: itself, or its wrap source
-      int is = ii;
-      if (a.f.x_wrap) {
-        if (ii == 0) is = nx - 2;
-        else if (ii == nx - 1) is = 1;
-      }
+      const int is = x_wrap_src(a, ii);
       const long long sdx = (long long)rr * nx + is;
       if (rr < 1 || rr > ny - 2 || is < 1 || is > nx - 2) {
         su[lr][lc] = a.u[sdx];  // closed halo: pre-update pass-through
@@ -1626,36 +1553,26 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
   }
   __syncthreads();
 
-  // pass 2, vector: friction of the fast output pairs from LDS
+  // pass 2, vector: friction of the fast output pairs from LDS (loop head
+  // as in sw_stage30t; a shared pass function changed the 512-thread
+  // variant's integer code)
   for (int t = tid; t < kTJ30 * kPC30; t += NT_) {
     const int ro = t / kPC30, po = t % kPC30;
     const int j = jb + ro;
     const int i0 = cb + 2 * po;
     if (!s30_fast_out(a, j, i0)) continue;  // scalar pass owns this pair
-    const int lr = ro + 1, x = 2 * po + 2;
     const long long idx = (long long)j * nx + i0;
-    // stage27_pair math, inputs from LDS
-    vf2 uw = {su[lr][x - 1], su[lr][x]}, uc = {su[lr][x], su[lr][x + 1]},
-        ue = {su[lr][x + 1], su[lr][x + 2]};
-    vf2 un = {su[lr + 1][x], su[lr + 1][x + 1]},
-        us = {su[lr - 1][x], su[lr - 1][x + 1]};
-    vf2 vw = {sv[lr][x - 1], sv[lr][x]}, vcc = {sv[lr][x], sv[lr][x + 1]},
-        ve = {sv[lr][x + 1], sv[lr][x + 2]};
-    vf2 vn = {sv[lr + 1][x], sv[lr + 1][x + 1]},
-        vs = {sv[lr - 1][x], sv[lr - 1][x + 1]};
-    const float nu = a.nu;
-    vf2 lu = (nu * (ue - uc) * a.rdx - nu * (uc - uw) * a.rdx) * a.rdx +
-             (nu * (un - uc) * a.rdy - nu * (uc - us) * a.rdy) * a.rdy;
-    vf2 lv = (nu * (ve - vcc) * a.rdx - nu * (vcc - vw) * a.rdx) * a.rdx +
-             (nu * (vn - vcc) * a.rdy - nu * (vcc - vs) * a.rdy) * a.rdy;
-    st2(a.u2, idx, uc + a.dt * lu);
-    st2(a.v2, idx, vcc + a.dt * lv);
+    const UV2 r = s30_friction_lds(a, su, sv, ro + 1, 2 * po + 2);
+    st2(a.u2, idx, r.u);
+    st2(a.v2, idx, r.v);
   }
 
   if (perim) {
     // pass 2, scalar: owned cells outside the s30_fast_out rectangle —
     // ringb_final_uv's friction (division form, wall masks) with the
-    // five inputs from LDS, plus the halo cells' end-of-step values
+    // five inputs from LDS, plus the halo cells' end-of-step values.
+    // A copy, not a shared function: every shared form tried reshuffled
+    // this kernel's register allocation and SGPR spills
     const S1Rect orc = s1_out_rect(ny, nx, a.f, jb, cb);
     const int r0 = orc.r0, r1 = orc.r1, c0 = orc.c0, c1 = orc.c1;
     const int nrim = s1_rim_count(kTJ30, 2 * kPC30, r0, r1, c0, c1);
@@ -1671,11 +1588,7 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
         // halo cell.  An x_wrap halo of an interior row is refreshed by
         // the owner of its wrap source (below); every other halo cell
         // passes the pre-update field through (x-wrapped at corners)
-        int is = i;
-        if (a.f.x_wrap) {
-          if (i == 0) is = nx - 2;
-          else if (i == nx - 1) is = 1;
-        }
+        const int is = x_wrap_src(a, i);
         if (is != i && j >= 1 && j <= ny - 2) continue;
         const long long sdx = (long long)j * nx + is;
         a.h2[idx] = a.h[sdx];
@@ -1767,421 +1680,91 @@ static void sw_fill_args(SwArgs<T>& a, const SwLaunchParams& p) {
          p.north_wall, p.x_wrap};
 }
 
+// scalar stages: one cell per thread, 1-D grid of row-major column-chunk
+// tiles with the XCD-aware remap applied inside the kernel (SW_BLOCK_MAP)
 template <typename T>
-static void sw_launch(int stage, const SwLaunchParams& p,
-                      hipStream_t stream) {
+static SwStageStatus sw_launch_cells(void (*kernel)(SwArgs<T>),
+                                     const SwLaunchParams& p,
+                                     hipStream_t stream) {
   SwArgs<T> a;
   sw_fill_args(a, p);
-  // one cell per thread; 1-D grid of row-major column-chunk tiles with
-  // the XCD-aware remap applied inside the kernel (SW_BLOCK_MAP)
-  long long gx = (p.nx + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(gx * p.ny)), block(kBlock);
-  switch (stage) {
-    case 1: hipLaunchKernelGGL(sw_stage1_kernel<T>, grid, block, 0, stream, a); break;
-    case 6: hipLaunchKernelGGL(sw_stage6_kernel<T>, grid, block, 0, stream, a); break;
-    case 7: hipLaunchKernelGGL(sw_stage7_kernel<T>, grid, block, 0, stream, a); break;
-    case 8: hipLaunchKernelGGL(sw_stage8_kernel<T>, grid, block, 0, stream, a); break;
-    default: break;
-  }
+  const long long gx = (p.nx + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(gx * p.ny)), dim3(kBlock), 0,
+                     stream, a);
+  return SW_STAGE_OK;
 }
+#define SW_CELLS(kernel)                                  \
+  (is_double ? sw_launch_cells(kernel<double>, p, stream) \
+             : sw_launch_cells(kernel<float>, p, stream))
 
-void launch_sw_stage(int stage, const SwLaunchParams& p, int is_double,
-                     hipStream_t stream) {
-  if (!is_double && stage >= 11) {
-    // vectorized float stages: 11 -> stage1v, 16 -> stage6v, 17 -> stage7v
-    SwArgs<float> a;
-    sw_fill_args(a, p);
-    long long ppr = stage >= 19 ? (p.nx + 1) / 2 : (p.nx + 3) / 4;
-    long long packs = ppr * p.ny;
-    dim3 grid((unsigned)((packs + 255) / 256)), block(256);
-    if (stage >= 21 && stage <= 23) {  // band-tiled: TJ = 4 / 8 / 16
-      int tjv = stage == 21 ? 4 : stage == 22 ? 8 : 16;
-      long long tpc = 256 / tjv;
-      long long tiles = ((p.ny + tjv - 1) / tjv) * ((ppr + tpc - 1) / tpc);
-      grid = dim3((unsigned)tiles);
+SwStageStatus launch_sw_stage(int stage, const SwLaunchParams& p,
+                              int is_double, hipStream_t stream) {
+  SwArgs<float> a;
+  if (!is_double) sw_fill_args(a, p);
+  // every vector / fused stage is float-only
+  auto f32 = [&](void (*kernel)(SwArgs<float>), long long blocks,
+                 int threads = 256) -> SwStageStatus {
+    if (is_double) return SW_STAGE_F32_ONLY;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0,
+                       stream, a);
+    return SW_STAGE_OK;
+  };
+  // blocks of 256 threads, one thread per pack of `cols` columns
+  auto packs = [&](int cols) {
+    return ((p.nx + cols - 1) / cols * p.ny + 255) / 256;
+  };
+  // band tiles of the 2-column update: tj rows x 256/tj pairs per block
+  auto band_tiles = [&](int tj) {
+    const long long ppr = (p.nx + 1) / 2, tpc = 256 / tj;
+    return ((p.ny + tj - 1) / tj) * ((ppr + tpc - 1) / tpc);
+  };
+  // the LDS tiles of sw_stage30t, and the s30_ring_cell enumeration
+  const long long tiles30 = ((p.nx + 2 * kPC30 - 1) / (2 * kPC30)) *
+                            ((p.ny + kTJ30 - 1) / kTJ30);
+  const long long ring_cells =
+      (p.ny < 8 ? p.ny : 8) * p.nx +
+      (p.ny > 8 ? (p.ny - 8) * (p.nx < 12 ? p.nx : 12) : 0);
+  const long long ring30 = (ring_cells + 255) / 256;
+
+  switch ((SwStage)stage) {
+    case SW_PRE_SCALAR: return SW_CELLS(sw_stage1_kernel);
+    case SW_UPDATE_SCALAR: return SW_CELLS(sw_stage6_kernel);
+    case SW_FRICTION_SCALAR: return SW_CELLS(sw_stage7_kernel);
+    case SW_UPDATE_MERGED_SCALAR: return SW_CELLS(sw_stage8_kernel);
+    case SW_PRE_V4: return f32(sw_stage1v, packs(4));
+    case SW_UPDATE_V4: return f32(sw_stage6v, packs(4));
+    case SW_FRICTION_V4: return f32(sw_stage7v, packs(4));
+    case SW_UPDATE_V4_MERGED: return f32(sw_stage18v, packs(4));
+    case SW_UPDATE_V2: return f32(sw_stage19t<false>, packs(2));
+    case SW_UPDATE_V2_NT: return f32(sw_stage19t<true>, packs(2));
+    case SW_UPDATE_V2_TILE4: return f32(sw_stage21t<4>, band_tiles(4));
+    case SW_UPDATE_V2_TILE8: return f32(sw_stage21t<8>, band_tiles(8));
+    case SW_UPDATE_V2_TILE16: return f32(sw_stage21t<16>, band_tiles(16));
+    case SW_FRICTION_V2: return f32(sw_stage27v, packs(2));
+    case SW_FRICTION_V2_INTERIOR: return f32(sw_stage28v, packs(2));
+    case SW_FRICTION_V2_RING: {  // the sw_stage29v enumeration
+      const long long mid = p.ny - 5 > 0 ? p.ny - 5 : 0;
+      return f32(sw_stage29v, (5 * ((p.nx + 1) / 2) + mid * 4 + 255) / 256);
     }
-    switch (stage) {
-      case 11: hipLaunchKernelGGL(sw_stage1v, grid, block, 0, stream, a); break;
-      case 16: hipLaunchKernelGGL(sw_stage6v, grid, block, 0, stream, a); break;
-      case 17: hipLaunchKernelGGL(sw_stage7v, grid, block, 0, stream, a); break;
-      case 18: hipLaunchKernelGGL(sw_stage18v, grid, block, 0, stream, a); break;
-      case 19: hipLaunchKernelGGL(sw_stage19t<false>, grid, block, 0, stream, a); break;
-      case 20: hipLaunchKernelGGL(sw_stage19t<true>, grid, block, 0, stream, a); break;
-      case 21: hipLaunchKernelGGL(sw_stage21t<4>, grid, block, 0, stream, a); break;
-      case 22: hipLaunchKernelGGL(sw_stage21t<8>, grid, block, 0, stream, a); break;
-      case 23: hipLaunchKernelGGL(sw_stage21t<16>, grid, block, 0, stream, a); break;
-      case 27: hipLaunchKernelGGL(sw_stage27v, grid, block, 0, stream, a); break;
-      case 30:
-      case 31: {  // the whole world-1 step in one launch; 31 = 512-thread
-                  // blocks (single-round LDS fill), same per-task code
-        const S1Tiles tl = s1_tiles((int)p.ny, (int)p.nx, a.f);
-        dim3 g1((unsigned)(tl.nper_pad + tl.nfast));
-        if (stage == 31) {
-          hipLaunchKernelGGL(sw_step1t<512>, g1, dim3(512), 0, stream, a);
-        } else {
-          hipLaunchKernelGGL(sw_step1t<256>, g1, block, 0, stream, a);
-        }
-        break;
-      }
-      case 34:    // 34 = the three-launch world-1 form (fast + ringA +
-                  // ringB through the fe/fn strip), kept for A/B runs
-      case 32: {  // 32 = fast + ringA only (N>1: a real fe/fn halo
-                  // exchange runs before ringB, launched as stage 33)
-        long long bpc = (p.nx + 2 * kPC30 - 1) / (2 * kPC30);
-        long long bands = (p.ny + kTJ30 - 1) / kTJ30;
-        dim3 g30((unsigned)(bpc * bands));
-        hipLaunchKernelGGL(sw_stage30t<256>, g30, block, 0, stream, a);
-        long long er = p.ny < 8 ? p.ny : 8, ec = p.nx < 12 ? p.nx : 12;
-        long long ring = er * p.nx +
-                         (p.ny > 8 ? (p.ny - 8) * ec : 0);
-        dim3 gcl((unsigned)((ring + 255) / 256));
-        hipLaunchKernelGGL(sw_stage30_ringA, gcl, block, 0, stream, a);
-        if (stage != 32) {
-          hipLaunchKernelGGL(sw_stage30_ringB, gcl, block, 0, stream, a);
-        }
-        break;
-      }
-      case 33: {  // ringB alone, after the fe/fn halo exchange
-        long long er = p.ny < 8 ? p.ny : 8, ec = p.nx < 12 ? p.nx : 12;
-        long long ring = er * p.nx +
-                         (p.ny > 8 ? (p.ny - 8) * ec : 0);
-        dim3 gcl((unsigned)((ring + 255) / 256));
-        hipLaunchKernelGGL(sw_stage30_ringB, gcl, block, 0, stream, a);
-        break;
-      }
-      case 28: hipLaunchKernelGGL(sw_stage28v, grid, block, 0, stream, a); break;
-      case 29: {
-        long long ppr2 = (p.nx + 1) / 2;
-        long long mid = p.ny - 5 > 0 ? p.ny - 5 : 0;
-        long long ring = 5 * ppr2 + mid * 4;
-        dim3 rg((unsigned)((ring + 255) / 256));
-        hipLaunchKernelGGL(sw_stage29v, rg, block, 0, stream, a);
-        break;
-      }
+    case SW_STEP1:      // the whole world-1 step in one launch
+    case SW_STEP1_512:  // 512-thread blocks (single-round LDS fill)
+    {
+      if (is_double) return SW_STAGE_F32_ONLY;
+      const S1Tiles tl = s1_tiles((int)p.ny, (int)p.nx, a.f);
+      return stage == SW_STEP1
+                 ? f32(sw_step1t<256>, tl.nper_pad + tl.nfast)
+                 : f32(sw_step1t<512>, tl.nper_pad + tl.nfast, 512);
     }
-    return;
-  }
-  if (is_double) {
-    sw_launch<double>(stage >= 11 ? stage - 10 : stage, p, stream);
-  } else {
-    sw_launch<float>(stage, p, stream);
-  }
-}
-
-// ---------------------------------------------------------------- halo ops
-// One kernel per exchange phase instead of torch narrow copies (measured
-// ~110 us/step of copyBuffer/elementwise time in the eager halo path).
-
-namespace {
-
-template <typename T>
-struct HaloArgs {
-  T* f0;
-  T* f1;
-  T* f2;
-  int nf, ny, nx;
-  int col;  // for pack/unpack
-};
-
-template <typename T>
-__device__ inline T* halo_field(const HaloArgs<T>& a, int f) {
-  return f == 0 ? a.f0 : (f == 1 ? a.f1 : a.f2);
-}
-
-// periodic self-wrap, side 0: east halo col nx-1 <- col 1 ("send west");
-// side 1: west halo col 0 <- col nx-2 ("send east")
-template <typename T>
-__global__ void halo_wrap_kernel(HaloArgs<T> a, int side) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nf * a.ny) return;
-  int f = t / a.ny, j = t % a.ny;
-  T* p = halo_field(a, f) + (long long)j * a.nx;
-  if (side != 1) p[a.nx - 1] = p[1];
-  if (side != 0) p[0] = p[a.nx - 2];  // side 2 = both wraps in one launch
-}
-
-template <typename T>
-__global__ void pack_cols_kernel(HaloArgs<T> a, T* buf) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nf * a.ny) return;
-  int f = t / a.ny, j = t % a.ny;
-  buf[t] = halo_field(a, f)[(long long)j * a.nx + a.col];
-}
-
-template <typename T>
-__global__ void unpack_cols_kernel(HaloArgs<T> a, const T* buf) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.nf * a.ny) return;
-  int f = t / a.ny, j = t % a.ny;
-  halo_field(a, f)[(long long)j * a.nx + a.col] = buf[t];
-}
-
-template <typename T>
-HaloArgs<T> make_halo_args(void* const* fields, int nf, long long ny,
-                           long long nx, long long col) {
-  HaloArgs<T> a;
-  a.f0 = (T*)fields[0];
-  a.f1 = nf > 1 ? (T*)fields[1] : (T*)fields[0];
-  a.f2 = nf > 2 ? (T*)fields[2] : (T*)fields[0];
-  a.nf = nf;
-  a.ny = (int)ny;
-  a.nx = (int)nx;
-  a.col = (int)col;
-  return a;
-}
-
-int halo_grid(int n) { return (n + kBlock - 1) / kBlock; }
-
-}  // namespace
-
-void launch_halo_wrap(void* const* fields, int nf, long long ny,
-                      long long nx, int side, int is_double,
-                      hipStream_t stream) {
-  int n = nf * (int)ny;
-  if (is_double) {
-    auto a = make_halo_args<double>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(halo_wrap_kernel<double>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, side);
-  } else {
-    auto a = make_halo_args<float>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(halo_wrap_kernel<float>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, side);
-  }
-}
-
-void launch_pack_cols(void* buf, void* const* fields, int nf, long long ny,
-                      long long nx, long long col, int is_double,
-                      hipStream_t stream) {
-  int n = nf * (int)ny;
-  if (is_double) {
-    auto a = make_halo_args<double>(fields, nf, ny, nx, col);
-    hipLaunchKernelGGL(pack_cols_kernel<double>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, (double*)buf);
-  } else {
-    auto a = make_halo_args<float>(fields, nf, ny, nx, col);
-    hipLaunchKernelGGL(pack_cols_kernel<float>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, (float*)buf);
-  }
-}
-
-void launch_unpack_cols(void* const* fields, const void* buf, int nf,
-                        long long ny, long long nx, long long col,
-                        int is_double, hipStream_t stream) {
-  int n = nf * (int)ny;
-  if (is_double) {
-    auto a = make_halo_args<double>(fields, nf, ny, nx, col);
-    hipLaunchKernelGGL(unpack_cols_kernel<double>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, (const double*)buf);
-  } else {
-    auto a = make_halo_args<float>(fields, nf, ny, nx, col);
-    hipLaunchKernelGGL(unpack_cols_kernel<float>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a, (const float*)buf);
-  }
-}
-
-// corner pack/unpack for the single-group halo exchange: buf layout is
-// [diag d][field f] with d: 0=to-SW/from-NE, 1=to-SE/from-NW,
-// 2=to-NW/from-SE, 3=to-NE/from-SW (matching parallel/grid.py halo_plan).
-namespace {
-
-template <typename T>
-__global__ void pack_corners_kernel(HaloArgs<T> a, T* buf) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 4 * a.nf) return;
-  int d = t / a.nf, f = t % a.nf;
-  const int ny = a.ny, nx = a.nx;
-  int j = (d < 2) ? 1 : ny - 2;
-  int i = (d == 0 || d == 2) ? 1 : nx - 2;
-  buf[t] = halo_field(a, f)[(long long)j * nx + i];
-}
-
-template <typename T>
-__global__ void unpack_corners_kernel(HaloArgs<T> a, const T* buf,
-                                      int mask) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 4 * a.nf) return;
-  int d = t / a.nf, f = t % a.nf;
-  if (!(mask & (1 << d))) return;
-  const int ny = a.ny, nx = a.nx;
-  // recv cells: d0 (ny-1,nx-1), d1 (ny-1,0), d2 (0,nx-1), d3 (0,0)
-  int j = (d < 2) ? ny - 1 : 0;
-  int i = (d == 0 || d == 2) ? nx - 1 : 0;
-  halo_field(a, f)[(long long)j * nx + i] = buf[t];
-}
-
-// merged staging: wrap + both column packs + corner pack in ONE launch
-// (work layout [wrap | cb0 | cb1 | corners]); see kernels.h for the
-// contract.  All segments touch disjoint cells: wrap writes halo cols
-// 0/nx-1, col packs read interior cols (1/nx-2), corner pack reads
-// interior corner cells.
-template <typename T>
-struct HaloXArgs {
-  T* f0;
-  T* f1;
-  T* f2;
-  int nf, ny, nx;
-  T* cb0;
-  T* cb1;
-  T* cor;
-  int c0, c1;
-  int wrap_side;  // -1 none, 0 east<-1, 1 west<-nx-2, 2 both
-  int cor_mask;
-};
-
-template <typename T>
-__device__ inline T* hx_field(const HaloXArgs<T>& a, int f) {
-  return f == 0 ? a.f0 : (f == 1 ? a.f1 : a.f2);
-}
-
-template <typename T>
-__global__ void pack_halo_kernel(HaloXArgs<T> a) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ncol = a.nf * a.ny;
-  if (t < ncol) {
-    if (a.wrap_side < 0) return;
-    int f = t / a.ny, j = t % a.ny;
-    T* p = hx_field(a, f) + (long long)j * a.nx;
-    if (a.wrap_side != 1) p[a.nx - 1] = p[1];
-    if (a.wrap_side != 0) p[0] = p[a.nx - 2];
-    return;
-  }
-  t -= ncol;
-  if (t < 2 * ncol) {
-    T* buf = t < ncol ? a.cb0 : a.cb1;
-    int col = t < ncol ? a.c0 : a.c1;
-    if (!buf) return;
-    int s = t % ncol;
-    int f = s / a.ny, j = s % a.ny;
-    buf[s] = hx_field(a, f)[(long long)j * a.nx + col];
-    return;
-  }
-  t -= 2 * ncol;
-  if (t >= 4 * a.nf || !a.cor) return;
-  int d = t / a.nf, f = t % a.nf;
-  int j = (d < 2) ? 1 : a.ny - 2;
-  int i = (d == 0 || d == 2) ? 1 : a.nx - 2;
-  a.cor[t] = hx_field(a, f)[(long long)j * a.nx + i];
-}
-
-// which corner diagonal writes cell (j in {0, ny-1}, col in {0, nx-1}):
-// d0 (ny-1,nx-1), d1 (ny-1,0), d2 (0,nx-1), d3 (0,0)
-__device__ inline int corner_diag(bool top_row, bool east_col) {
-  return top_row ? (east_col ? 0 : 1) : (east_col ? 2 : 3);
-}
-
-template <typename T>
-__global__ void unpack_halo_kernel(HaloXArgs<T> a) {
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ncol = a.nf * a.ny;
-  if (t < 2 * ncol) {
-    const T* buf = t < ncol ? a.cb0 : a.cb1;
-    int col = t < ncol ? a.c0 : a.c1;
-    if (!buf) return;
-    int s = t % ncol;
-    int f = s / a.ny, j = s % a.ny;
-    if ((j == 0 || j == a.ny - 1) && a.cor) {
-      // the corner segment of this same launch owns this cell
-      int d = corner_diag(j == a.ny - 1, col == a.nx - 1);
-      if (a.cor_mask & (1 << d)) return;
+    case SW_FUSED_FAST_RINGA:  // multi-rank: a real fe/fn strip exchange
+                               // runs before SW_FUSED_RINGB
+    case SW_FUSED_RING3: {     // the three-launch world-1 form (A/B runs)
+      SwStageStatus rc = f32(sw_stage30t<256>, tiles30);
+      if (!rc) rc = f32(sw_stage30_ringA, ring30);
+      if (!rc && stage == SW_FUSED_RING3) rc = f32(sw_stage30_ringB, ring30);
+      return rc;
     }
-    hx_field(a, f)[(long long)j * a.nx + col] = buf[s];
-    return;
+    case SW_FUSED_RINGB: return f32(sw_stage30_ringB, ring30);
   }
-  t -= 2 * ncol;
-  if (t >= 4 * a.nf || !a.cor) return;
-  int d = t / a.nf, f = t % a.nf;
-  if (!(a.cor_mask & (1 << d))) return;
-  int j = (d < 2) ? a.ny - 1 : 0;
-  int i = (d == 0 || d == 2) ? a.nx - 1 : 0;
-  hx_field(a, f)[(long long)j * a.nx + i] = a.cor[t];
+  return SW_STAGE_UNKNOWN;
 }
-
-template <typename T>
-HaloXArgs<T> make_hx_args(void* const* fields, int nf, long long ny,
-                          long long nx, int wrap_side, void* cb0,
-                          long long c0, void* cb1, long long c1, void* cor,
-                          int cor_mask) {
-  HaloXArgs<T> a;
-  a.f0 = (T*)fields[0];
-  a.f1 = nf > 1 ? (T*)fields[1] : (T*)fields[0];
-  a.f2 = nf > 2 ? (T*)fields[2] : (T*)fields[0];
-  a.nf = nf;
-  a.ny = (int)ny;
-  a.nx = (int)nx;
-  a.cb0 = (T*)cb0;
-  a.cb1 = (T*)cb1;
-  a.cor = (T*)cor;
-  a.c0 = (int)c0;
-  a.c1 = (int)c1;
-  a.wrap_side = wrap_side;
-  a.cor_mask = cor_mask;
-  return a;
-}
-
-}  // namespace
-
-void launch_pack_corners(void* buf, void* const* fields, int nf,
-                         long long ny, long long nx, int is_double,
-                         hipStream_t stream) {
-  int n = 4 * nf;
-  if (is_double) {
-    auto a = make_halo_args<double>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(pack_corners_kernel<double>, dim3(1), dim3(64), 0,
-                       stream, a, (double*)buf);
-  } else {
-    auto a = make_halo_args<float>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(pack_corners_kernel<float>, dim3(1), dim3(64), 0,
-                       stream, a, (float*)buf);
-  }
-  (void)n;
-}
-
-void launch_unpack_corners(void* const* fields, const void* buf, int nf,
-                           long long ny, long long nx, int mask,
-                           int is_double, hipStream_t stream) {
-  if (is_double) {
-    auto a = make_halo_args<double>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(unpack_corners_kernel<double>, dim3(1), dim3(64), 0,
-                       stream, a, (const double*)buf, mask);
-  } else {
-    auto a = make_halo_args<float>(fields, nf, ny, nx, 0);
-    hipLaunchKernelGGL(unpack_corners_kernel<float>, dim3(1), dim3(64), 0,
-                       stream, a, (const float*)buf, mask);
-  }
-}
-
-void launch_pack_halo(void* const* fields, int nf, long long ny,
-                      long long nx, int wrap_side, void* cb0, long long c0,
-                      void* cb1, long long c1, void* cor, int is_double,
-                      hipStream_t stream) {
-  int n = 3 * nf * (int)ny + 4 * nf;
-  if (is_double) {
-    auto a = make_hx_args<double>(fields, nf, ny, nx, wrap_side, cb0, c0,
-                                  cb1, c1, cor, 0);
-    hipLaunchKernelGGL(pack_halo_kernel<double>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a);
-  } else {
-    auto a = make_hx_args<float>(fields, nf, ny, nx, wrap_side, cb0, c0,
-                                 cb1, c1, cor, 0);
-    hipLaunchKernelGGL(pack_halo_kernel<float>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a);
-  }
-}
-
-void launch_unpack_halo(void* const* fields, int nf, long long ny,
-                        long long nx, void* cb0, long long c0, void* cb1,
-                        long long c1, void* cor, int cor_mask,
-                        int is_double, hipStream_t stream) {
-  int n = 2 * nf * (int)ny + 4 * nf;
-  if (is_double) {
-    auto a = make_hx_args<double>(fields, nf, ny, nx, -1, cb0, c0, cb1, c1,
-                                  cor, cor_mask);
-    hipLaunchKernelGGL(unpack_halo_kernel<double>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a);
-  } else {
-    auto a = make_hx_args<float>(fields, nf, ny, nx, -1, cb0, c0, cb1, c1,
-                                 cor, cor_mask);
-    hipLaunchKernelGGL(unpack_halo_kernel<float>, dim3(halo_grid(n)),
-                       dim3(kBlock), 0, stream, a);
-  }
-}
+#undef SW_CELLS

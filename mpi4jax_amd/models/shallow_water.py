@@ -14,19 +14,19 @@ day is the headline metric.
 
 Two step implementations share semantics: an eager torch-op path (CPU
 and reference/debugging) and the fused MI355X path — by default ONE
-LDS-tiled update+friction pass (stage 30: at world 1 a single kernel
-launch is the whole model step, boundary tiles and the periodic wrap
-refresh included, with zero exchange kernels; stage 32, multi-rank: the
-pass plus two boundary-ring kernels with a two-field u'/v'-strip
-exchange between them), with the
-two-kernel pipeline (stage 19 tendencies+update, stage 27 friction,
-selectable variants and scalar fallbacks) behind MPI4JAX_AMD_SW_NOFUSE,
-a one-native-call halo exchange (merged pack launch, single RCCL group,
+LDS-tiled update+friction pass (at world 1 a single kernel launch is the
+whole model step, with zero exchange kernels; multi-rank: the pass plus
+two boundary-ring kernels with a two-field u'/v'-strip exchange between
+them), with the two-kernel pipeline behind MPI4JAX_AMD_SW_NOFUSE, a
+one-native-call halo exchange (merged pack launch, single RCCL group,
 merged unpack launch), and validated hipGraph capture for multistep
-replay at any world size.
+replay at any world size.  docs/developers.md tabulates every stage
+(:class:`SwStage`), its kernels and the env knob that selects it.
 """
 
+import enum
 import math
+import os
 import time
 from collections import namedtuple
 
@@ -45,6 +45,29 @@ CORIOLIS_BETA = 2e-11
 ADAMS_BASHFORTH_A = 1.5 + 0.1
 ADAMS_BASHFORTH_B = -(0.5 + 0.1)
 
+
+
+# Launchable kernel stages, one family per line — mirrors `enum SwStage` in
+# csrc/kernels.h (ext.sw_stage_ids()); the values are public.
+SwStage = enum.IntEnum("SwStage", dict(
+    SW_PRE_SCALAR=1, SW_UPDATE_SCALAR=6, SW_FRICTION_SCALAR=7,
+    SW_UPDATE_MERGED_SCALAR=8,
+    SW_PRE_V4=11, SW_UPDATE_V4=16, SW_FRICTION_V4=17, SW_UPDATE_V4_MERGED=18,
+    SW_UPDATE_V2=19, SW_UPDATE_V2_NT=20,
+    SW_UPDATE_V2_TILE4=21, SW_UPDATE_V2_TILE8=22, SW_UPDATE_V2_TILE16=23,
+    SW_FRICTION_V2=27, SW_FRICTION_V2_INTERIOR=28, SW_FRICTION_V2_RING=29,
+    SW_STEP1=30, SW_STEP1_512=31,
+    SW_FUSED_FAST_RINGA=32, SW_FUSED_RINGB=33, SW_FUSED_RING3=34,
+))
+_S = SwStage
+# MPI4JAX_AMD_SW_TILE value -> band-tiled update stage (TJ rows per block)
+_TILE_STAGE = {"4": _S.SW_UPDATE_V2_TILE4, "8": _S.SW_UPDATE_V2_TILE8,
+               "16": _S.SW_UPDATE_V2_TILE16}
+_STAGE_BUFS = ("fe fn q ke h u v dn_h dn_u dn_v do_h do_u do_v "
+               "h_alt u_alt v_alt").split()  # sw_stage buffer order
+# main stages that are a complete model step in one native call
+_SINGLE_CALL = (_S.SW_STEP1, _S.SW_STEP1_512, _S.SW_FUSED_RING3)
+
 _I = slice(1, -1)  # interior
 _L = slice(None, -2)  # shifted left/down
 _R = slice(2, None)  # shifted right/up
@@ -62,6 +85,8 @@ class ShallowWater:
         device / dtype: tensor placement (float32 matches the reference).
         periodic_x: periodic east-west boundary (reference default True).
     """
+
+    _force_remote_exchange = False  # test hook, see _exchange_cache
 
     def __init__(self, nx=360, ny=180, dx=5e3, dy=5e3, *, comm=None,
                  dims=None, device="cpu", dtype=torch.float32,
@@ -246,65 +271,48 @@ class ShallowWater:
             fb[k], fb[f"{k}_alt"] = fb[f"{k}_alt"], fb[k]
 
     def _stage_plan(self):
-        """Kernel-id triple for the (pre-tendency, tendency, friction)
-        stages — static per (dtype, env) so it is resolved once at buffer
-        init, not per step.
-
-        float32 runs the vectorized stage kernels (2 columns/thread by
-        default — the measured-fastest occupancy point); f64 and the
-        MPI4JAX_AMD_SW_NOVEC escape hatch run the scalar ones.  The
-        other variants (4-col, nontemporal, two-pass, fully-merged
-        scalar) stay selectable for measurement — see
-        profiles/README.md for the numbers behind the default.
+        """Stage triple (pre-tendency, tendency, friction; None = no such
+        launch) — static per (dtype, env), so resolved once at buffer
+        init.  The first matching row wins.  float32 defaults to the fused
+        update+friction step (equal to the two-kernel path up to
+        FMA-contraction rounding); every other variant stays selectable
+        for measurement: docs/developers.md has the table,
+        profiles/README.md the numbers behind the default.
         """
-        import os
-
-        if os.environ.get("MPI4JAX_AMD_SW_MERGED"):
-            return None, 8, 7
-        if (self.dtype == torch.float32
-                and not os.environ.get("MPI4JAX_AMD_SW_NOVEC")):
-            if os.environ.get("MPI4JAX_AMD_SW_TWOPASS"):
-                return 11, 16, 17
-            if os.environ.get("MPI4JAX_AMD_SW_4COL"):
-                return None, 18, 17  # 4-col variants (4 waves/SIMD)
-            if os.environ.get("MPI4JAX_AMD_SW_NT"):
-                return None, 20, 27  # + nontemporal streaming hints
-            tile = os.environ.get("MPI4JAX_AMD_SW_TILE", "")
-            if tile in ("4", "8", "16"):
-                # band-tiled tendency kernel: TJ rows per 256-thread block
-                return None, {"4": 21, "8": 22, "16": 23}[tile], 27
-            if (self.lateral_viscosity > 0
-                    and not os.environ.get("MPI4JAX_AMD_SW_OVERLAP")
-                    and os.environ.get("MPI4JAX_AMD_SW_NOFUSE") != "1"):
-                # update+friction fused — drops the u'/v' intermediate
-                # round trip (4 of 16 field passes); equivalent to the
-                # two-kernel path to FMA-contraction rounding
-                # (tests/test_gpu_ops.py::test_stage30_*).  s7=None
-                # marks the world-1 shape: the whole step is ONE kernel
-                # launch (boundary tiles recompute their own u'/v'
-                # apron, in-kernel wrap refresh, zero exchange
-                # launches); MPI4JAX_AMD_SW_RING3=1 selects the earlier
-                # three-launch form (fast + ringA + ringB through the
-                # fe/fn strip) for A/B measurement.  s7=33 is the
-                # multi-rank shape (a real fe/fn strip exchange between
-                # ringA and ringB).
-                if (self.grid.nproc_y * self.grid.nproc_x == 1
-                        and not self._force_remote_exchange):
-                    if os.environ.get("MPI4JAX_AMD_SW_RING3") == "1":
-                        return None, 34, None  # three-launch form
-                    if os.environ.get("MPI4JAX_AMD_SW_FUSE512") == "1":
-                        return None, 31, None  # 512-thread variant
-                    return None, 30, None
-                return None, 32, 33
+        env = os.environ.get
+        vec = self.dtype == torch.float32 and not env("MPI4JAX_AMD_SW_NOVEC")
+        fuse = (self.lateral_viscosity > 0
+                and not env("MPI4JAX_AMD_SW_OVERLAP")
+                and env("MPI4JAX_AMD_SW_NOFUSE") != "1")
+        local = (self.grid.nproc_y * self.grid.nproc_x == 1
+                 and not self._force_remote_exchange)
+        tile = _TILE_STAGE.get(env("MPI4JAX_AMD_SW_TILE", ""))
+        table = (
+            (env("MPI4JAX_AMD_SW_MERGED"),
+             (None, _S.SW_UPDATE_MERGED_SCALAR, _S.SW_FRICTION_SCALAR)),
+            (not vec,
+             (_S.SW_PRE_SCALAR, _S.SW_UPDATE_SCALAR, _S.SW_FRICTION_SCALAR)),
+            (env("MPI4JAX_AMD_SW_TWOPASS"),
+             (_S.SW_PRE_V4, _S.SW_UPDATE_V4, _S.SW_FRICTION_V4)),
+            (env("MPI4JAX_AMD_SW_4COL"),  # 4-col variants (4 waves/SIMD)
+             (None, _S.SW_UPDATE_V4_MERGED, _S.SW_FRICTION_V4)),
+            (env("MPI4JAX_AMD_SW_NT"),
+             (None, _S.SW_UPDATE_V2_NT, _S.SW_FRICTION_V2)),
+            (tile, (None, tile, _S.SW_FRICTION_V2)),
+            (fuse and not local,
+             (None, _S.SW_FUSED_FAST_RINGA, _S.SW_FUSED_RINGB)),
+            (fuse and env("MPI4JAX_AMD_SW_RING3") == "1",
+             (None, _S.SW_FUSED_RING3, None)),
+            (fuse and env("MPI4JAX_AMD_SW_FUSE512") == "1",
+             (None, _S.SW_STEP1_512, None)),
+            (fuse, (None, _S.SW_STEP1, None)),
             # 2-col merged single pass: 68 VGPRs -> 7 waves/SIMD, measured
-            # fastest (stage18v parks ~48% of cycles on memory at 4 waves)
-            return None, 19, 27
-        return 1, 6, 7
+            # fastest (the 4-col one parks ~48% of cycles on memory)
+            (True, (None, _S.SW_UPDATE_V2, _S.SW_FRICTION_V2)),
+        )
+        return next(plan for cond, plan in table if cond)
 
     def _step_fused(self, state, first_step=False):
-        from .._backend import rccl
-
-        ext = rccl.ext()
         fb = self._fb
         if fb is None or state.h is not fb["h"]:
             self._init_fused_buffers(state)
@@ -312,93 +320,87 @@ class ShallowWater:
         # step-invariant host work is resolved once per buffer (re)init
         const = fb.get("step_const")
         if const is None:
+            plan = self._stage_plan()
+            shape = (self._step_single if plan[1] in _SINGLE_CALL
+                     else self._step_ring
+                     if plan[1] == _S.SW_FUSED_FAST_RINGA
+                     else self._step_pipeline)
             const = fb["step_const"] = (
                 self._fused_flags(),
                 float(CORIOLIS_F + float(self.y_local[0]) * CORIOLIS_BETA),
                 float(self.dy * CORIOLIS_BETA),
-                self._stage_plan(),
+                plan, shape,
             )
-        flags, cor_base, cor_dj, (s1, s6, s7) = const
-        ab_a, ab_b = ((1.0, 0.0) if first_step
-                      else (ADAMS_BASHFORTH_A, ADAMS_BASHFORTH_B))
-
-        def stage(n):
-            bufs = [fb["fe"], fb["fn"], fb["q"], fb["ke"], fb["h"],
-                    fb["u"], fb["v"], fb["dn_h"], fb["dn_u"], fb["dn_v"],
-                    fb["do_h"], fb["do_u"], fb["do_v"], fb["h_alt"],
-                    fb["u_alt"], fb["v_alt"]]
-            ext.sw_stage(n, bufs, self.dx, self.dy, self.dt,
-                         self.lateral_viscosity, cor_base, cor_dj, ab_a,
-                         ab_b, flags)
-
-        if s1 is not None:
-            stage(s1)     # fe, fn, q, ke (with open-edge halo formulas)
-        if s6 in (30, 31, 34):
-            # fused update+friction: u'/v' never round-trip through HBM,
-            # the mid-step exchange disappears, and the kernel writes
-            # the end-of-step wrap refresh itself — a complete model
-            # step with zero exchange launches (30/31: one launch; 34:
-            # the three-launch form)
-            stage(s6)
-            self._swap("h", "u", "v")
-            for k in ("h", "u", "v"):
-                fb[f"do_{k}"], fb[f"dn_{k}"] = fb[f"dn_{k}"], fb[f"do_{k}"]
-            return ModelState(fb["h"], fb["u"], fb["v"], fb["do_h"],
-                              fb["do_u"], fb["do_v"])
-        if s6 == 32:
-            # multi-rank fused step: the friction's only remote need is
-            # the u'/v' boundary strip (staged in fe/fn) — exchange
-            # those two fields between the ring kernels, then refresh
-            # the finals' halos once at the end
-            stage(s6)     # fast kernel + ringA (completes the strip)
-            self._exchange_fields([fb["fe"], fb["fn"]])
-            stage(s7)     # ringB: ring friction from the strip
-            self._swap("h", "u", "v")
-            self._exchange_fields([fb["h"], fb["u"], fb["v"]])
-            for k in ("h", "u", "v"):
-                fb[f"do_{k}"], fb[f"dn_{k}"] = fb[f"dn_{k}"], fb[f"do_{k}"]
-            return ModelState(fb["h"], fb["u"], fb["v"], fb["do_h"],
-                              fb["do_u"], fb["do_v"])
-        stage(s6)         # tendencies + time update -> h_alt/u_alt/v_alt
-        self._swap("h", "u", "v")
-        if self._overlap_plan() is not None and self.lateral_viscosity > 0:
-            # halo/compute overlap (MPI4JAX_AMD_SW_OVERLAP=1): run the
-            # h/u/v exchange on a second stream while the main stream
-            # computes the halo-independent friction pairs (stage 28);
-            # the halo-dependent ring (stage 29) joins after.  28+29 use
-            # the identical per-pair code as stage 27, so the step is
-            # bitwise equal to the serial path.
-            s28, s29, comm_stream, ev1, ev2 = self._overlap_plan()
-            main = torch.cuda.current_stream()
-            ev1.record(main)
-            comm_stream.wait_event(ev1)
-            with torch.cuda.stream(comm_stream):
-                self._exchange_fields([fb["h"], fb["u"], fb["v"]])
-            stage(s28)    # deep interior, overlapped with the exchange
-            ev2.record(comm_stream)
-            main.wait_event(ev2)
-            stage(s29)    # boundary ring, needs the fresh halos
-            self._swap("u", "v")
-            self._exchange_fields([fb["u"], fb["v"]])
-        else:
-            self._exchange_fields([fb["h"], fb["u"], fb["v"]])
-            if self.lateral_viscosity > 0:
-                stage(s7)     # friction Laplacian update -> u_alt/v_alt
-                self._swap("u", "v")
-                self._exchange_fields([fb["u"], fb["v"]])
+        self._ab = ((1.0, 0.0) if first_step
+                    else (ADAMS_BASHFORTH_A, ADAMS_BASHFORTH_B))
+        const[4](*const[3])  # ends with the new h/u/v in place, halos fresh
         # the new tendencies become "old" for the next step
         for k in ("h", "u", "v"):
             fb[f"do_{k}"], fb[f"dn_{k}"] = fb[f"dn_{k}"], fb[f"do_{k}"]
         return ModelState(fb["h"], fb["u"], fb["v"], fb["do_h"], fb["do_u"],
                           fb["do_v"])
 
+    def _launch(self, stage):
+        from .._backend import rccl
+
+        fb = self._fb
+        flags, cor_base, cor_dj = fb["step_const"][:3]
+        rccl.ext().sw_stage(stage, [fb[k] for k in _STAGE_BUFS], self.dx,
+                            self.dy, self.dt, self.lateral_viscosity,
+                            cor_base, cor_dj, *self._ab, flags)
+
+    def _step_single(self, pre, main, friction):
+        # fused update+friction, end-of-step wrap refresh included: a
+        # complete model step with zero exchange launches
+        self._launch(main)
+        self._swap("h", "u", "v")
+
+    def _step_ring(self, pre, main, friction):
+        # multi-rank fused step: the friction's only remote need is the
+        # u'/v' boundary strip (staged in fe/fn) — exchange those two
+        # fields between the ring kernels, the finals' halos at the end
+        fb = self._fb
+        self._launch(main)      # fast kernel + ringA (completes the strip)
+        self._exchange_fields([fb["fe"], fb["fn"]])
+        self._launch(friction)  # ringB: ring friction from the strip
+        self._swap("h", "u", "v")
+        self._exchange_fields([fb["h"], fb["u"], fb["v"]])
+
+    def _step_pipeline(self, pre, main, friction):
+        fb = self._fb
+        if pre is not None:
+            self._launch(pre)  # fe, fn, q, ke (with open-edge halo formulas)
+        self._launch(main)  # tendencies + time update -> h_alt/u_alt/v_alt
+        self._swap("h", "u", "v")
+        overlap = self._overlap_plan() if self.lateral_viscosity > 0 else None
+        if overlap is None:
+            self._exchange_fields([fb["h"], fb["u"], fb["v"]])
+            if self.lateral_viscosity <= 0:
+                return
+            self._launch(friction)  # friction update -> u_alt/v_alt
+        else:
+            # MPI4JAX_AMD_SW_OVERLAP=1: the h/u/v exchange runs on a
+            # second stream under the halo-independent friction pairs;
+            # the halo-dependent ring joins after.  Same per-pair code as
+            # SW_FRICTION_V2, so bitwise equal to the serial path.
+            interior, ring, comm_stream, ev1, ev2 = overlap
+            main_stream = torch.cuda.current_stream()
+            ev1.record(main_stream)
+            comm_stream.wait_event(ev1)
+            with torch.cuda.stream(comm_stream):
+                self._exchange_fields([fb["h"], fb["u"], fb["v"]])
+            self._launch(interior)  # overlapped with the exchange
+            ev2.record(comm_stream)
+            main_stream.wait_event(ev2)
+            self._launch(ring)      # needs the fresh halos
+        self._swap("u", "v")
+        self._exchange_fields([fb["u"], fb["v"]])
+
     # ------------------------------------------------------------------
     def _overlap_plan(self):
-        """(interior_stage, ring_stage, comm_stream) when the overlap path
-        is enabled and applicable (float32 vector path, GPU), else None.
-        Cached with the fused buffers."""
-        import os
-
+        """(interior_stage, ring_stage, comm_stream, event, event) when
+        the overlap path is enabled and applicable (float32 vector path,
+        GPU), else None.  Cached with the fused buffers."""
         fb = self._fb
         if "overlap_plan" in fb:
             return fb["overlap_plan"]
@@ -406,8 +408,9 @@ class ShallowWater:
         if (os.environ.get("MPI4JAX_AMD_SW_OVERLAP") == "1"
                 and self.dtype == torch.float32
                 and self.device.type == "cuda"
-                and self._stage_plan()[2] == 27):
-            plan = (28, 29, torch.cuda.Stream(), torch.cuda.Event(),
+                and self._stage_plan()[2] == _S.SW_FRICTION_V2):
+            plan = (_S.SW_FRICTION_V2_INTERIOR, _S.SW_FRICTION_V2_RING,
+                    torch.cuda.Stream(), torch.cuda.Event(),
                     torch.cuda.Event())
         fb["overlap_plan"] = plan
         return plan
@@ -430,7 +433,7 @@ class ShallowWater:
         fb["cor_rbuf"] = torch.empty_like(fb["cor_sbuf"])
         (wrap_sides, col_ops, row_ops, cor_ops,
          cor_mask) = halo_exchange_schedule(self.grid, nx, ny)
-        if getattr(self, "_force_remote_exchange", False) and wrap_sides:
+        if self._force_remote_exchange and wrap_sides:
             # test hook: express the periodic self-wraps as remote
             # transfers to self so the full RCCL exchange path (pack,
             # grouped p2p, unpack) runs at world 1 — used by the overlap
@@ -466,8 +469,6 @@ class ShallowWater:
         not host-bound; MPI4JAX_AMD_SW_PYEXCHANGE selects the
         wire-identical per-op Python executor instead.
         """
-        import os
-
         from .._backend import rccl
 
         cache = self._exchange_cache()
@@ -543,8 +544,6 @@ class ShallowWater:
         (wire-identical) eager loop.  ``MPI4JAX_AMD_SW_GRAPH=0`` forces
         the eager loop.
         """
-        import os
-
         env = os.environ.get("MPI4JAX_AMD_SW_GRAPH", "").strip()
         if use_graph is None:
             use_graph = (self.fused and self.device.type == "cuda"

@@ -152,3 +152,26 @@ def test_single_launch_graph_replay_matches_plain_steps(monkeypatch):
         out[graphed] = _snap(st)
     for name in FIELDS:
         assert torch.equal(out[False][name], out[True][name]), name
+
+
+def test_stage_dispatch_is_explicit():
+    """The native stage table equals the Python enum, and a launch the
+    table cannot serve raises without launching anything: an id that is
+    no stage, and a float32-only stage handed float64 buffers."""
+    from mpi4jax_amd._backend import rccl
+    from mpi4jax_amd.models.shallow_water import SwStage
+
+    ext = rccl.ext()
+    assert ext.sw_stage_ids() == {s.name: int(s) for s in SwStage}
+
+    def call(stage, dtype):
+        bufs = [torch.full((10, 34), 7.0, dtype=dtype, device="cuda")
+                for _ in range(16)]
+        with pytest.raises(RuntimeError):
+            ext.sw_stage(stage, bufs, 5e3, 5e3, 10.0, 1.0, 2e-4, 1e-7, 1.0,
+                         0.0, [0, 0, 1, 1, 0, 1, 1])
+        torch.cuda.synchronize()
+        assert all(bool((b == 7.0).all()) for b in bufs)
+
+    call(9, torch.float32)
+    call(30, torch.float64)

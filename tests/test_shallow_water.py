@@ -232,6 +232,36 @@ def test_stage_plan_selection(monkeypatch):
     assert sw64._stage_plan() == (1, 6, 7)
 
 
+def test_stage_ids_are_pinned():
+    """The stage ids are public (profiles/ and the docs cite them): the
+    Python enum must keep exactly these names and values."""
+    from mpi4jax_amd.models.shallow_water import SwStage
+
+    assert {s.name: int(s) for s in SwStage} == {
+        "SW_PRE_SCALAR": 1,
+        "SW_UPDATE_SCALAR": 6,
+        "SW_FRICTION_SCALAR": 7,
+        "SW_UPDATE_MERGED_SCALAR": 8,
+        "SW_PRE_V4": 11,
+        "SW_UPDATE_V4": 16,
+        "SW_FRICTION_V4": 17,
+        "SW_UPDATE_V4_MERGED": 18,
+        "SW_UPDATE_V2": 19,
+        "SW_UPDATE_V2_NT": 20,
+        "SW_UPDATE_V2_TILE4": 21,
+        "SW_UPDATE_V2_TILE8": 22,
+        "SW_UPDATE_V2_TILE16": 23,
+        "SW_FRICTION_V2": 27,
+        "SW_FRICTION_V2_INTERIOR": 28,
+        "SW_FRICTION_V2_RING": 29,
+        "SW_STEP1": 30,
+        "SW_STEP1_512": 31,
+        "SW_FUSED_FAST_RINGA": 32,
+        "SW_FUSED_RINGB": 33,
+        "SW_FUSED_RING3": 34,
+    }
+
+
 def test_exchange_cache_flat_encoding():
     """The flattened int schedule handed to the native sw_exchange must
     encode exactly the Python schedule with None -> -1, for every
