@@ -5,7 +5,9 @@
     ``CartesianGrid.halo_exchange_`` on the same tensors, the path the
     library offered before the exchanger existed;
 (b) one float32 field (8, 1806, 3606), width 3: the native executor
-    against the Python executor of the same exchanger.
+    against the Python executor of the same exchanger;
+(c) ``adjoint_`` (the backward pass of ``exchange_ad``) against
+    ``exchange_`` on the same exchanger, for both configurations above.
 
 Per case: wall time per exchange (host clock around a loop that ends in a
 device synchronise) and host enqueue time per exchange (a short burst
@@ -16,7 +18,10 @@ contenders are checked to produce bitwise-identical fields.
 
 Run on a GPU box:  python benchmarks/bench_halo.py [--out result.json]
 ``--profile-a N`` runs only N native exchanges of case (a) after a
-warm-up — the body of a ``rocprofv3 --kernel-trace --stats`` run.
+warm-up — the body of a ``rocprofv3 --kernel-trace --stats`` run;
+``--profile-c N`` does the same for the adjoint of that configuration
+(besides the warm-up, the run holds the one exchange and one adjoint of
+the dot-product check).
 """
 
 import argparse
@@ -114,6 +119,37 @@ def case_b(grid):
             "python_executor": py}
 
 
+def case_c(grid, shape, width, nfields):
+    """``adjoint_`` against ``exchange_`` on the same exchanger.  The two
+    move the same staging bytes; the adjoint's accumulate kernel visits
+    the 2*width-thick frame, about twice the cells of the unpack."""
+    torch.manual_seed(2)
+    fields = [torch.randn(shape, device="cuda") for _ in range(nfields)]
+    ex = grid.make_halo_exchanger(shape, torch.float32, "cuda", width=width,
+                                  nfields=nfields)
+    # <exchange(x), y> == <x, adjoint(y)> first, in float64 on the host
+    ys = [torch.randn(shape, device="cuda") for _ in range(nfields)]
+    fx = ex.exchange(*fields)
+    ay = ex.adjoint(*ys)
+    fx, ay = [(t,) if isinstance(t, torch.Tensor) else t for t in (fx, ay)]
+    lhs = sum((a.double() * b.double()).sum().item() for a, b in zip(fx, ys))
+    rhs = sum((a.double() * b.double()).sum().item()
+              for a, b in zip(fields, ay))
+    assert abs(lhs - rhs) <= 1e-5 * max(1.0, abs(lhs)), (lhs, rhs)
+    # repeated adjoints of the same tensors grow without bound (each
+    # wrap adds a term), so the timed adjoint runs on zeros
+    grads = [torch.zeros(shape, device="cuda") for _ in range(nfields)]
+    return {"exchange_": lambda: ex.exchange_(*fields),
+            "adjoint_": lambda: ex.adjoint_(*grads)}
+
+
+def _ratio(res):
+    res["adjoint_over_exchange_wall"] = round(
+        res["adjoint_"]["wall_us_per_exchange"]
+        / res["exchange_"]["wall_us_per_exchange"], 3)
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--warmup", type=int, default=50)
@@ -121,6 +157,9 @@ def main():
     p.add_argument("--burst", type=int, default=50)
     p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--profile-a", type=int, default=0)
+    p.add_argument("--profile-c", type=int, default=0)
+    p.add_argument("--cases", default="abc",
+                   help="which cases to run, e.g. 'c' (default: all)")
     p.add_argument("--out", default=None,
                    help="also write the JSON result to this file")
     args = p.parse_args()
@@ -140,12 +179,29 @@ def main():
         print(f"profiled {args.profile_a} native exchanges of case (a)")
         return
 
+    if args.profile_c:
+        fns = case_c(grid, (1802, 3602), 1, 3)
+        fns["adjoint_"]()  # warm-up: loads the code object
+        torch.cuda.synchronize()
+        for _ in range(args.profile_c):
+            fns["adjoint_"]()
+        torch.cuda.synchronize()
+        print(f"profiled {args.profile_c} native adjoints of case (c), "
+              f"3 x (1802, 3602)")
+        return
+
     out = {"device": torch.cuda.get_device_name(0),
            "iters": args.iters, "repeats": args.repeats}
-    out["a_3xf32_1802x3602_w1"] = _compare(
-        case_a(grid)[2], args.warmup, args.iters, args.burst, args.repeats)
-    out["b_1xf32_8x1806x3606_w3"] = _compare(
-        case_b(grid), args.warmup, args.iters, args.burst, args.repeats)
+    run = (args.warmup, args.iters, args.burst, args.repeats)
+    if "a" in args.cases:
+        out["a_3xf32_1802x3602_w1"] = _compare(case_a(grid)[2], *run)
+    if "b" in args.cases:
+        out["b_1xf32_8x1806x3606_w3"] = _compare(case_b(grid), *run)
+    if "c" in args.cases:
+        out["c_adjoint_3xf32_1802x3602_w1"] = _ratio(_compare(
+            case_c(grid, (1802, 3602), 1, 3), *run))
+        out["c_adjoint_1xf32_8x1806x3606_w3"] = _ratio(_compare(
+            case_c(grid, (8, 1806, 3606), 3, 1), *run))
     print(json.dumps(out, indent=2))
     if args.out:
         os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)

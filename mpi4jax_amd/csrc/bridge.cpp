@@ -32,6 +32,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "halo_geom.h"
 #include "kernels.h"
 
 namespace {
@@ -932,6 +933,84 @@ void sw_exchange(std::vector<at::Tensor> fields,
   watchdog_arm("sw_exchange", c.rank, stream);
 }
 
+struct HaloNdPlan {
+  int64_t nf, w, esz, total;
+  HaloGeom g;
+  bool any_remote;
+  void* fptr[kHaloMaxFields];
+};
+
+// Argument checks and slot geometry shared by halo_exchange_nd and
+// halo_adjoint_nd (`who` names the entry in the one message that does).
+HaloNdPlan halo_nd_plan(const char* who,
+                        const std::vector<at::Tensor>& fields,
+                        int64_t levels, int64_t ny, int64_t nx,
+                        int64_t width, const std::vector<int64_t>& send_to,
+                        const std::vector<int64_t>& recv_from,
+                        int64_t local_mask, const at::Tensor& sbuf,
+                        const at::Tensor& rbuf) {
+  HaloNdPlan p{};
+  const int64_t nf = (int64_t)fields.size();
+  TORCH_CHECK(1 <= nf && nf <= kHaloMaxFields, "1..", kHaloMaxFields,
+              " halo fields supported, got ", nf);
+  TORCH_CHECK(send_to.size() == kHaloDirs && recv_from.size() == kHaloDirs,
+              who, " expects 8 send and 8 recv peers");
+  const int64_t w = width;
+  TORCH_CHECK(w >= 1 && levels >= 1 && ny >= 3 * w && nx >= 3 * w,
+              "bad halo geometry: levels ", levels, ", ny ", ny, ", nx ", nx,
+              ", width ", w, " (each axis needs n >= 3*width)");
+  TORCH_CHECK(levels < ((int64_t)1 << 31) && ny < ((int64_t)1 << 31) &&
+                  nx < ((int64_t)1 << 31),
+              "halo extents must be below 2^31");
+  const at::Tensor& f0 = fields[0];
+  const int64_t esz = f0.element_size();
+  TORCH_CHECK(esz == 1 || esz == 2 || esz == 4 || esz == 8,
+              "halo exchange supports 1/2/4/8-byte elements, got ", esz);
+  TORCH_CHECK(levels <= f0.numel() && f0.numel() / levels == ny * nx &&
+                  f0.numel() % levels == 0,
+              "halo field has ", f0.numel(), " elements, expected ", levels,
+              " x ", ny, " x ", nx);
+  for (int64_t k = 0; k < nf; ++k) {
+    const auto& f = fields[k];
+    TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
+                    f.numel() == f0.numel() &&
+                    f.scalar_type() == f0.scalar_type() &&
+                    f.device() == f0.device(),
+                "bad halo field ", k);
+    p.fptr[k] = f.data_ptr();
+  }
+
+  // slot geometry: [0] columns W/E, [2] rows N/S, [4] corners
+  p.g = halo_geometry(nf, levels, ny, nx, w);
+  const int64_t total = p.g.total;
+  TORCH_CHECK(total < ((int64_t)1 << 31),
+              "halo staging of ", total, " elements exceeds 2^31");
+  for (const at::Tensor* b : {&sbuf, &rbuf}) {
+    TORCH_CHECK(b->is_cuda() && b->is_contiguous() &&
+                    b->device() == f0.device() &&
+                    b->element_size() == esz && b->numel() >= total,
+                "bad halo staging buffer (need ", total, " elements of ",
+                esz, " bytes on the fields' device)");
+  }
+  TORCH_CHECK(0 <= local_mask && local_mask < (1 << kHaloDirs),
+              "bad halo local mask");
+
+  for (int i = 0; i < kHaloDirs; ++i) {
+    TORCH_CHECK(send_to[i] >= -1 && recv_from[i] >= -1, "bad halo peer");
+    if ((local_mask >> i) & 1) {
+      TORCH_CHECK(send_to[i] >= 0 && recv_from[i] >= 0,
+                  "local halo entry ", i, " needs both peers");
+    } else {
+      p.any_remote |= send_to[i] >= 0 || recv_from[i] >= 0;
+    }
+  }
+  p.nf = nf;
+  p.w = w;
+  p.esz = esz;
+  p.total = total;
+  return p;
+}
+
 // Native executor of parallel/halo.HaloExchanger: one pack launch, one
 // RCCL group, one unpack launch, for `levels` x (ny, nx) fields with a
 // `width`-cell halo.  Entry i of send_to / recv_from (-1 = no peer) is
@@ -952,80 +1031,18 @@ void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
                       std::vector<int64_t> recv_from, int64_t local_mask,
                       at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_exchange_nd");
-  const int64_t nf = (int64_t)fields.size();
-  TORCH_CHECK(1 <= nf && nf <= kHaloMaxFields, "1..", kHaloMaxFields,
-              " halo fields supported, got ", nf);
-  TORCH_CHECK(send_to.size() == kHaloDirs && recv_from.size() == kHaloDirs,
-              "halo_exchange_nd expects 8 send and 8 recv peers");
-  const int64_t w = width;
-  TORCH_CHECK(w >= 1 && levels >= 1 && ny >= 3 * w && nx >= 3 * w,
-              "bad halo geometry: levels ", levels, ", ny ", ny, ", nx ", nx,
-              ", width ", w, " (each axis needs n >= 3*width)");
-  TORCH_CHECK(levels < ((int64_t)1 << 31) && ny < ((int64_t)1 << 31) &&
-                  nx < ((int64_t)1 << 31),
-              "halo extents must be below 2^31");
-  const at::Tensor& f0 = fields[0];
-  const int64_t esz = f0.element_size();
-  TORCH_CHECK(esz == 1 || esz == 2 || esz == 4 || esz == 8,
-              "halo exchange supports 1/2/4/8-byte elements, got ", esz);
-  TORCH_CHECK(levels <= f0.numel() && f0.numel() / levels == ny * nx &&
-                  f0.numel() % levels == 0,
-              "halo field has ", f0.numel(), " elements, expected ", levels,
-              " x ", ny, " x ", nx);
-  HaloNdArgs pk{}, un{};
-  for (int64_t k = 0; k < nf; ++k) {
-    const auto& f = fields[k];
-    TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
-                    f.numel() == f0.numel() &&
-                    f.scalar_type() == f0.scalar_type() &&
-                    f.device() == f0.device(),
-                "bad halo field ", k);
-    pk.f[k] = un.f[k] = f.data_ptr();
-  }
-
-  // slot geometry: [0] columns W/E, [2] rows N/S, [4] corners
-  const int64_t dirs[kHaloDirs][2] = {{0, -1}, {0, 1},  {1, 0},  {-1, 0},
-                                      {-1, -1}, {-1, 1}, {1, -1}, {1, 1}};
-  int64_t slot_off[kHaloDirs + 1];
-  int64_t sy[kHaloDirs], sx[kHaloDirs], ry[kHaloDirs], rx[kHaloDirs];
-  int64_t hh[kHaloDirs], ww[kHaloDirs];
-  slot_off[0] = 0;
-  for (int i = 0; i < kHaloDirs; ++i) {
-    const int64_t dy = dirs[i][0], dx = dirs[i][1];
-    // y: a column strip (dy == 0) is full height
-    sy[i] = dy < 0 ? w : (dy > 0 ? ny - 2 * w : 0);
-    ry[i] = dy < 0 ? ny - w : 0;
-    hh[i] = dy != 0 ? w : ny;
-    // x: a row strip (dx == 0) covers the interior columns
-    sx[i] = dx < 0 ? w : (dx > 0 ? nx - 2 * w : w);
-    rx[i] = dx < 0 ? nx - w : (dx > 0 ? 0 : w);
-    ww[i] = dx != 0 ? w : nx - 2 * w;
-    slot_off[i + 1] = slot_off[i] + nf * levels * hh[i] * ww[i];
-  }
-  const int64_t total = slot_off[kHaloDirs];
-  TORCH_CHECK(total < ((int64_t)1 << 31),
-              "halo staging of ", total, " elements exceeds 2^31");
-  for (const at::Tensor* b : {&sbuf, &rbuf}) {
-    TORCH_CHECK(b->is_cuda() && b->is_contiguous() &&
-                    b->device() == f0.device() &&
-                    b->element_size() == esz && b->numel() >= total,
-                "bad halo staging buffer (need ", total, " elements of ",
-                esz, " bytes on the fields' device)");
-  }
-  TORCH_CHECK(0 <= local_mask && local_mask < (1 << kHaloDirs),
-              "bad halo local mask");
-
-  bool any_remote = false;
+  const HaloNdPlan plan =
+      halo_nd_plan("halo_exchange_nd", fields, levels, ny, nx, width,
+                   send_to, recv_from, local_mask, sbuf, rbuf);
+  const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
+  const int64_t total = plan.total;
+  const bool any_remote = plan.any_remote;
+  const int64_t* slot_off = plan.g.slot_off;
+  const int64_t *sy = plan.g.sy, *sx = plan.g.sx, *ry = plan.g.ry,
+                *rx = plan.g.rx, *hh = plan.g.hh, *ww = plan.g.ww;
   auto is_local = [&](int i) { return (local_mask >> i) & 1; };
-  for (int i = 0; i < kHaloDirs; ++i) {
-    TORCH_CHECK(send_to[i] >= -1 && recv_from[i] >= -1, "bad halo peer");
-    if (is_local(i)) {
-      TORCH_CHECK(send_to[i] >= 0 && recv_from[i] >= 0,
-                  "local halo entry ", i, " needs both peers");
-    } else {
-      any_remote |= send_to[i] >= 0 || recv_from[i] >= 0;
-    }
-  }
+  HaloNdArgs pk{}, un{};
+  for (int64_t k = 0; k < nf; ++k) pk.f[k] = un.f[k] = plan.fptr[k];
 
   char* sb = (char*)sbuf.data_ptr();
   char* rb = (char*)rbuf.data_ptr();
@@ -1106,6 +1123,128 @@ void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
   }
 }
 
+// Adjoint of halo_exchange_nd, in place on the gradients `fields`; same
+// arguments, same slots, the schedule run backwards.  The forward pass is
+// a gather (every output cell reads one input cell), so the adjoint is a
+// scatter-add:
+//   1. pack: the RECEIVE window of every entry with a receiver goes into
+//      slot i; the rows of a column slot that a present corner entry
+//      owned in the forward pass carry zeros;
+//   2. one RCCL group with the peers' roles swapped: slot i is sent to
+//      recv_from[i] and received from send_to[i], in the same entry
+//      order, so message i still pairs with message i.  A local entry is
+//      packed straight into the receive staging slot.  No group when
+//      nothing is remote;
+//   3. accumulate (halo_adjoint_acc_kernel): every receive window with a
+//      receiver is zeroed and received slot i is added into the SEND
+//      window of entry i.  Send windows overlap, so the kernel works per
+//      field cell and gathers that cell's terms, last entry first.
+// Floating dtypes only: step 3 is arithmetic.
+void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
+                     int64_t ny, int64_t nx, int64_t width,
+                     std::vector<int64_t> send_to,
+                     std::vector<int64_t> recv_from, int64_t local_mask,
+                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_adjoint_nd");
+  const HaloNdPlan plan =
+      halo_nd_plan("halo_adjoint_nd", fields, levels, ny, nx, width,
+                   send_to, recv_from, local_mask, sbuf, rbuf);
+  const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
+  const HaloGeom& g = plan.g;
+  const auto st = fields[0].scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
+                  st == at::kBFloat16,
+              "halo adjoint supports float16, bfloat16, float32 and "
+              "float64, got ", st);
+  TORCH_CHECK(sbuf.scalar_type() == st && rbuf.scalar_type() == st,
+              "halo adjoint staging buffers must have the fields' dtype");
+  const HaloFrame fr = halo_frame(ny, nx, w);
+  const int64_t work = nf * levels * fr.per_level;
+  TORCH_CHECK_VALUE(work < ((int64_t)1 << 31), "halo adjoint over ", work,
+                    " frame cells exceeds the 2^31 work-item limit");
+  auto is_local = [&](int i) { return (local_mask >> i) & 1; };
+
+  char* sb = (char*)sbuf.data_ptr();
+  char* rb = (char*)rbuf.data_ptr();
+  HaloNdArgs pk{};
+  HaloAdjArgs ac{};
+  for (int64_t k = 0; k < nf; ++k) pk.f[k] = ac.f[k] = plan.fptr[k];
+  pk.ny = ac.ny = ny;
+  pk.nx = ac.nx = nx;
+  pk.levels = ac.levels = (unsigned)levels;
+  pk.nf = ac.nf = (int)nf;
+  pk.w = ac.w = (int)w;
+  int npk = 0;
+  unsigned pos = 0;
+  for (int i = 0; i < kHaloDirs; ++i) {
+    const int64_t n = g.slot_off[i + 1] - g.slot_off[i];
+    if (recv_from[i] >= 0) {
+      HaloNdSeg& s = pk.seg[npk++];
+      s.buf = (is_local(i) ? rb : sb) + g.slot_off[i] * esz;
+      s.y0 = g.ry[i];
+      s.x0 = g.rx[i];
+      s.h = (unsigned)g.hh[i];
+      s.wd = (unsigned)g.ww[i];
+      s.start = pos;
+      pos += (unsigned)n;
+      s.end = pos;
+      s.skip_lo = s.skip_hi = 0;
+      if (i < 2) {  // as in halo_exchange_nd's unpack: corners won
+        const int lo = i == 0 ? 6 : 7, hi = i == 0 ? 4 : 5;
+        s.skip_lo = recv_from[lo] >= 0;
+        s.skip_hi = recv_from[hi] >= 0;
+      }
+    }
+    HaloAdjSeg& a = ac.seg[i];
+    a.buf = rb + g.slot_off[i] * esz;
+    a.sy = (int)g.sy[i];
+    a.sx = (int)g.sx[i];
+    a.ry = (int)g.ry[i];
+    a.rx = (int)g.rx[i];
+    a.h = (unsigned)g.hh[i];
+    a.wd = (unsigned)g.ww[i];
+    a.acc = send_to[i] >= 0;
+    a.zero = recv_from[i] >= 0;
+  }
+  pk.total = pos;
+  for (int i = npk; i < kHaloDirs; ++i) pk.seg[i].end = pk.total;
+  ac.full = fr.full;
+  ac.band = fr.full ? 0u : (unsigned)fr.band;  // 2 * band <= per_level
+  ac.per_level = (unsigned)fr.per_level;
+  ac.total = (unsigned)work;
+
+  hipStream_t stream = cur_stream();
+  launch_halo_nd(pk, 2, (int)esz, stream);
+
+  if (plan.any_remote) {
+    auto c = get_comm(comm_id);
+    for (int i = 0; i < kHaloDirs; ++i) {
+      TORCH_CHECK(send_to[i] < c.size && recv_from[i] < c.size,
+                  "halo peer out of range for communicator of size ",
+                  c.size);
+    }
+    log_enqueue("HaloAdjointNd", c, plan.total);
+    RCCL_CHECK(ncclGroupStart());
+    for (int i = 0; i < kHaloDirs; ++i) {
+      if (is_local(i)) continue;
+      const int64_t nbytes = (g.slot_off[i + 1] - g.slot_off[i]) * esz;
+      if (recv_from[i] >= 0) {
+        p2p_send(sb + g.slot_off[i] * esz, nbytes, ncclUint8, 1,
+                 (int)recv_from[i], c.comm, stream);
+      }
+      if (send_to[i] >= 0) {
+        p2p_recv(rb + g.slot_off[i] * esz, nbytes, ncclUint8, 1,
+                 (int)send_to[i], c.comm, stream);
+      }
+    }
+    RCCL_CHECK(ncclGroupEnd());
+    launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
+    watchdog_arm("halo_adjoint_nd", c.rank, stream);
+  } else {
+    launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
+  }
+}
+
 // direct access to the combine kernel (used by gpu numerics tests)
 void combine(at::Tensor dst, at::Tensor a, at::Tensor b, int64_t op) {
   check_pair(dst, a);
@@ -1162,4 +1301,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_halo", &pack_halo);
   m.def("unpack_halo", &unpack_halo);
   m.def("halo_exchange_nd", &halo_exchange_nd);
+  m.def("halo_adjoint_nd", &halo_adjoint_nd);
 }

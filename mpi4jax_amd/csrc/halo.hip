@@ -17,6 +17,13 @@
 // Elements are moved as raw 1/2/4/8-byte words — any dtype of that size
 // travels.  Staging indices are 32-bit (the host checks the staging size);
 // every offset into a field is 64-bit.
+//
+// The exchange's adjoint (HaloExchanger.adjoint_) packs the RECEIVE
+// windows of the gradient with the same kernel (a third mode stores zeros
+// for the rows an unpack skips) and then runs halo_adjoint_acc_kernel, the
+// one typed kernel here: send windows overlap, so a field cell collects
+// up to 9 terms and the work item is the field cell, which gathers them —
+// no atomics, no race, a fixed order of adds.
 
 #include "kernels.h"
 
@@ -26,7 +33,9 @@ namespace {
 
 constexpr int kHaloBlock = 256;
 
-template <typename T, bool UNPACK>
+// ZPACK (with UNPACK false) is the adjoint's pack: the rows an unpack
+// would skip carry a zero word instead of the field's value.
+template <typename T, bool UNPACK, bool ZPACK = false>
 __global__ __launch_bounds__(kHaloBlock) void halo_nd_kernel(HaloNdArgs a) {
   const unsigned t = blockIdx.x * (unsigned)kHaloBlock + threadIdx.x;
   if (t >= a.total) return;
@@ -47,6 +56,13 @@ __global__ __launch_bounds__(kHaloBlock) void halo_nd_kernel(HaloNdArgs a) {
     if (sg.skip_lo && r < (unsigned)a.w) return;
     if (sg.skip_hi && r >= sg.h - (unsigned)a.w) return;
   }
+  if (ZPACK) {
+    if ((sg.skip_lo && r < (unsigned)a.w) ||
+        (sg.skip_hi && r >= sg.h - (unsigned)a.w)) {
+      ((T*)sg.buf)[s] = 0;
+      return;
+    }
+  }
   const long long off =
       ((long long)l * a.ny + sg.y0 + r) * a.nx + sg.x0 + c;
   T* field = (T*)a.f[f];
@@ -61,7 +77,10 @@ __global__ __launch_bounds__(kHaloBlock) void halo_nd_kernel(HaloNdArgs a) {
 template <typename T>
 void launch_t(const HaloNdArgs& a, int unpack, hipStream_t stream) {
   dim3 grid((a.total + kHaloBlock - 1) / kHaloBlock), block(kHaloBlock);
-  if (unpack) {
+  if (unpack == 2) {
+    hipLaunchKernelGGL((halo_nd_kernel<T, false, true>), grid, block, 0,
+                       stream, a);
+  } else if (unpack) {
     hipLaunchKernelGGL((halo_nd_kernel<T, true>), grid, block, 0, stream, a);
   } else {
     hipLaunchKernelGGL((halo_nd_kernel<T, false>), grid, block, 0, stream,
@@ -69,7 +88,109 @@ void launch_t(const HaloNdArgs& a, int unpack, hipStream_t stream) {
   }
 }
 
+// ---- adjoint accumulate: typed, one work item per frame cell
+
+struct Bf16 {
+  uint16_t bits;
+};
+
+template <typename T, typename Acc>
+__device__ inline Acc adj_load(const T* p) {
+  return (Acc)*p;
+}
+template <>
+__device__ inline float adj_load<Bf16, float>(const Bf16* p) {
+  return __uint_as_float((uint32_t)p->bits << 16);
+}
+
+template <typename T, typename Acc>
+__device__ inline void adj_store(T* p, Acc v) {
+  *p = (T)v;  // float -> _Float16 rounds to nearest even
+}
+template <>
+__device__ inline void adj_store<Bf16, float>(Bf16* p, float v) {
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) {
+    p->bits = 0x7fc0;  // NaN
+  } else {
+    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even
+    p->bits = (uint16_t)(u >> 16);
+  }
+}
+
+template <typename T, typename Acc>
+__global__ __launch_bounds__(kHaloBlock) void halo_adjoint_acc_kernel(
+    HaloAdjArgs a) {
+  const unsigned t = blockIdx.x * (unsigned)kHaloBlock + threadIdx.x;
+  if (t >= a.total) return;
+  const unsigned fl = t / a.per_level;  // field * levels + level
+  unsigned c = t - fl * a.per_level;
+  const unsigned f = fl / a.levels;
+  const unsigned l = fl - f * a.levels;
+  const unsigned nx = (unsigned)a.nx, ny = (unsigned)a.ny;
+  const unsigned w2 = 2u * (unsigned)a.w;
+  // frame cell -> (y, x); lanes sweep rows of the top / bottom bands
+  unsigned y, x;
+  if (a.full) {
+    y = c / nx;
+    x = c - y * nx;
+  } else if (c < 2u * a.band) {
+    y = c / nx;
+    x = c - y * nx;
+    if (y >= w2) y += ny - 2u * w2;  // bottom band
+  } else {
+    c -= 2u * a.band;
+    const unsigned sw = 2u * w2;  // west 2w columns, then east 2w
+    const unsigned r = c / sw;
+    const unsigned xx = c - r * sw;
+    y = w2 + r;
+    x = xx < w2 ? xx : nx - sw + xx;
+  }
+  bool zero = false, any = false;
+#pragma unroll
+  for (int i = 0; i < kHaloDirs; ++i) {
+    const HaloAdjSeg& sg = a.seg[i];
+    zero |= sg.zero && y - (unsigned)sg.ry < sg.h &&
+            x - (unsigned)sg.rx < sg.wd;
+  }
+  T* p = (T*)a.f[f] + (((long long)l * a.ny + y) * a.nx + x);
+  Acc sum = zero ? Acc(0) : adj_load<T, Acc>(p);
+  // fixed term order, the entries backwards (corners, S, N, E, W): every
+  // executor adds alike, and it is the order in which reverse-mode
+  // autodiff through the forward pass's sequence of writes adds them
+#pragma unroll
+  for (int i = kHaloDirs - 1; i >= 0; --i) {
+    const HaloAdjSeg& sg = a.seg[i];
+    const unsigned dy = y - (unsigned)sg.sy, dx = x - (unsigned)sg.sx;
+    if (sg.acc && dy < sg.h && dx < sg.wd) {
+      const unsigned s = (fl * sg.h + dy) * sg.wd + dx;  // < slot size
+      sum += adj_load<T, Acc>((const T*)sg.buf + s);
+      any = true;
+    }
+  }
+  if (zero || any) adj_store<T, Acc>(p, sum);
+}
+
+template <typename T, typename Acc>
+void launch_adj_t(const HaloAdjArgs& a, hipStream_t stream) {
+  dim3 grid((a.total + kHaloBlock - 1) / kHaloBlock), block(kHaloBlock);
+  hipLaunchKernelGGL((halo_adjoint_acc_kernel<T, Acc>), grid, block, 0,
+                     stream, a);
+}
+
 }  // namespace
+
+void launch_halo_adjoint_acc(const HaloAdjArgs& a, int dt_code,
+                             hipStream_t stream) {
+  if (a.total == 0) return;
+  switch (dt_code) {
+    case DT_F32: launch_adj_t<float, float>(a, stream); break;
+    case DT_F64: launch_adj_t<double, double>(a, stream); break;
+    case DT_F16: launch_adj_t<_Float16, float>(a, stream); break;
+    case DT_BF16: launch_adj_t<Bf16, float>(a, stream); break;
+    default: break;  // rejected by the host-side check in bridge.cpp
+  }
+}
 
 void launch_halo_nd(const HaloNdArgs& a, int unpack, int elem_size,
                     hipStream_t stream) {

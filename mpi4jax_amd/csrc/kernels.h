@@ -142,10 +142,10 @@ void launch_unpack_halo(void* const* fields, int nf, long long ny,
 // moves up to kHaloDirs segments; each segment is a (h, wd) window of
 // every level of every field, laid out [field][level][row][col] in its
 // staging slot.  Segments are compacted to the front; unused ones carry
-// end == total.  skip_lo / skip_hi (unpack only) make a full-height column
-// strip leave its first / last `w` rows to a corner segment of the same
-// launch.  Staging indices are 32-bit (total < 2^31, checked by the
-// caller); offsets into a field are 64-bit.
+// end == total.  skip_lo / skip_hi (a plain pack ignores them) make a
+// full-height column strip leave its first / last `w` rows to a corner
+// segment of the same launch.  Staging indices are 32-bit (total < 2^31,
+// checked by the caller); offsets into a field are 64-bit.
 constexpr int kHaloMaxFields = 8;
 constexpr int kHaloDirs = 8;
 
@@ -165,7 +165,41 @@ struct HaloNdArgs {
   int nf, w;
 };
 
-// unpack == 0: staging <- fields; unpack != 0: fields <- staging.
+// unpack == 0: staging <- fields; unpack == 1: fields <- staging;
+// unpack == 2: the adjoint's pack — staging <- fields, except that the
+// skip_lo / skip_hi rows store a zero word (the forward unpack never wrote
+// those cells from this slot, so no gradient flows back through them).
 // elem_size must be 1, 2, 4 or 8.
 void launch_halo_nd(const HaloNdArgs& a, int unpack, int elem_size,
                     hipStream_t stream);
+
+// Accumulate step of the halo exchange's adjoint (halo.hip).  One work
+// item per cell of the 2*w-thick frame (halo_geom.h: halo_frame) of every
+// level of every field.  The item starts from its own cell — or from 0
+// when the cell lies in a receive window with `zero` set, because the
+// forward exchange overwrote it — and adds, from the last entry to the
+// first, the staging element of every entry with `acc` set whose send
+// window holds the cell.
+// float16 / bfloat16 sum in float32 and round once at the store.  Work and
+// staging indices are 32-bit (total < 2^31, checked by the caller);
+// offsets into a field are 64-bit.
+struct HaloAdjSeg {
+  const void* buf;  // received slot of this entry, [field][level][row][col]
+  int sy, sx;       // send-window origin: where the terms are added
+  int ry, rx;       // receive-window origin: what is zeroed
+  unsigned h, wd;   // window size
+  int acc, zero;
+};
+
+struct HaloAdjArgs {
+  void* f[kHaloMaxFields];
+  HaloAdjSeg seg[kHaloDirs];
+  long long ny, nx;
+  unsigned levels, total;    // total = nf * levels * per_level
+  unsigned per_level, band;  // see HaloFrame
+  int nf, w, full;
+};
+
+// dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16.
+void launch_halo_adjoint_acc(const HaloAdjArgs& a, int dt_code,
+                             hipStream_t stream);

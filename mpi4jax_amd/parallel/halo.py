@@ -46,14 +46,54 @@ Executors:
   ``sendrecv`` / ``send`` / ``recv`` per schedule entry — the same message
   sizes in the same order.
 
-The exchanger is NOT differentiable (it mutates staging buffers and, for
-``exchange_``, the fields); use ``CartesianGrid.halo_exchange`` under
-autograd.
+Autodiff.  ``exchange`` and ``exchange_`` are NOT differentiable (they
+mutate staging buffers and, for ``exchange_``, the fields) and reject a
+field that requires grad.  ``exchange_ad`` is the differentiable
+out-of-place exchange: same values as ``exchange``, with a backward pass
+that runs the exchange's adjoint.  The adjoint is also public as
+``adjoint`` / ``adjoint_`` for adjoint-method solvers that call it
+directly.  Floating dtypes only (float16, bfloat16, float32, float64).
+
+The forward exchange is a gather — every output cell reads exactly one
+pre-exchange cell, a sender's source cell or itself — so the adjoint is a
+scatter-add with the message directions reversed:
+
+1. the RECEIVE window of every entry that has a receiver is packed into
+   slot *i* (for a column entry, the corner rows that a present corner
+   entry owned in the forward pass are packed as zeros);
+2. slot *i* is sent to ``recv_from[i]`` and received from ``send_to[i]``,
+   in the same fixed entry order;
+3. every receive window that has a receiver is zeroed (the forward pass
+   overwrote those cells, so nothing flows through them), and received
+   slot *i* is added into the SEND window of entry *i*.
+
+Send windows overlap (a column strip is full height; rows and corner
+blocks lie inside it), so one cell collects up to 9 terms.  Every executor
+forms that sum in the same order — the cell's own value (or 0 if it was
+overwritten), then the received terms in REVERSE :data:`DIRECTIONS` order
+(corners, S, N, E, W) — float32 / float64 in their own precision, float16
+/ bfloat16 in float32 with one rounding at the store.  The executors
+therefore agree bitwise.  The reverse order is the one reverse-mode
+autodiff uses on the forward pass's sequence of writes, so at ``width=1``
+the gradient is bitwise that of autograd through
+``CartesianGrid.halo_exchange``.
+A halo cell at a closed edge has no sender: the forward pass keeps it, and
+its gradient passes straight through.
+
+**The backward pass is a collective.**  Every rank must run it, and the
+exchanges must be differentiated in the reverse of their forward order.
+Both follow automatically when every rank runs the same program and every
+rank's loss depends on its exchanged fields; a rank that skips
+``backward()`` (or an ``exchange_ad`` none of whose inputs requires grad
+on one rank only) leaves its neighbours waiting.  Use
+``CartesianGrid.halo_exchange`` when a one-cell, one-field exchange
+composed of ``sendrecv`` is all that is needed.
 """
 
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 # (dy, dx); y grows northward, x eastward (CartesianGrid convention).
 # Columns (W, E), rows (N, S), corners — the order of grid.halo_plan.
@@ -64,6 +104,9 @@ DIRECTIONS = (
 )
 
 MAX_FIELDS = 8
+
+# dtypes of exchange_ad and the adjoint (the accumulate step is arithmetic)
+AD_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
 
 
 def _axis(d, n, w, full):
@@ -163,6 +206,16 @@ class HaloExchanger:
                 f"executor's 2^31 limit")
         self._sbuf = torch.empty(off, dtype=dtype, device=self.device)
         self._rbuf = torch.empty(off, dtype=dtype, device=self.device)
+        # work items of the native adjoint's accumulate kernel: one per
+        # cell of the 2*width-thick frame (the whole level when an axis
+        # is shorter than 4*width); checked when the adjoint is called.
+        # The same formula as halo_frame() in csrc/halo_geom.h, which
+        # halo_adjoint_nd checks again: change the two together.
+        if ny < 4 * w or nx < 4 * w:
+            frame = ny * nx
+        else:
+            frame = 4 * w * nx + (ny - 4 * w) * 4 * w
+        self._adj_work = nfields * levels * frame
 
     # ------------------------------------------------------------------
     @property
@@ -180,8 +233,17 @@ class HaloExchanger:
                 for e in self._entries
                 if e["send_to"] is not None or e["recv_from"] is not None]
 
+    def adjoint_schedule(self):
+        """The mirror of :meth:`schedule` for :meth:`adjoint_`: the same
+        entries in the same order with the roles swapped — the adjoint
+        sends slot *i* to the forward pass's ``recv_from`` and receives it
+        from the forward pass's ``send_to``."""
+        return [(e["direction"], e["recv_from"], e["send_to"], e["n"])
+                for e in self._entries
+                if e["send_to"] is not None or e["recv_from"] is not None]
+
     # ------------------------------------------------------------------
-    def _check(self, fields):
+    def _check(self, fields, allow_grad=False):
         if len(fields) != self.nfields:
             raise ValueError(
                 f"exchanger was built for {self.nfields} field(s), got "
@@ -204,11 +266,19 @@ class HaloExchanger:
                     f"for {self._sbuf.device}")
             if not f.is_contiguous():
                 raise ValueError(f"field {k} must be contiguous")
-            if f.requires_grad:
+            if f.requires_grad and not allow_grad:
+                # exchange / exchange_ / adjoint / adjoint_ mutate in
+                # place; exchange_ad is the differentiable entry
                 raise ValueError(
                     f"field {k} requires grad: the halo exchanger is not "
                     f"differentiable — use CartesianGrid.halo_exchange "
-                    f"under autograd")
+                    f"under autograd, or HaloExchanger.exchange_ad")
+
+    def _check_ad_dtype(self, what):
+        if self.dtype not in AD_DTYPES:
+            raise TypeError(
+                f"{what} supports float16, bfloat16, float32 and float64; "
+                f"this exchanger was built for {self.dtype}")
 
     def exchange(self, *fields):
         """Exchange copies of ``fields``; the inputs are never mutated.
@@ -227,7 +297,124 @@ class HaloExchanger:
             self._exchange_py(fields)
         return fields[0] if len(fields) == 1 else fields
 
+    def exchange_ad(self, *fields):
+        """Differentiable out-of-place exchange: the values of
+        :meth:`exchange`, and a backward pass that runs :meth:`adjoint_`
+        on the incoming gradients.  Fields may require grad.  The backward
+        pass is a collective (see the module docstring) and is once
+        differentiable."""
+        self._check_ad_dtype("exchange_ad")
+        self._check(fields, allow_grad=True)
+        out = _ExchangeAD.apply(self, *fields)
+        return out[0] if len(out) == 1 else out
+
+    def adjoint(self, *grads):
+        """Adjoint of the exchange on copies of ``grads`` (gradients with
+        respect to the exchange's outputs); the inputs are never mutated.
+        Returns the gradients with respect to the exchange's inputs: one
+        new tensor for one field, else a tuple."""
+        self._check_ad_dtype("adjoint")
+        self._check(grads)
+        return self.adjoint_(*(g.clone() for g in grads))
+
+    def adjoint_(self, *grads):
+        """In-place adjoint.  Returns the gradient (one) or the tuple of
+        gradients it was given.  A collective, like the exchange."""
+        self._check_ad_dtype("adjoint_")
+        self._check(grads)
+        if (self.device.type == "cuda"
+                and not os.environ.get("MPI4JAX_AMD_HALO_PY")):
+            if self._adj_work >= 1 << 31:
+                raise ValueError(
+                    f"halo adjoint over {self._adj_work} frame cells "
+                    f"exceeds the native executor's 2^31 limit")
+            self._adjoint_native(grads)
+        else:
+            self._adjoint_py(grads)
+        return grads[0] if len(grads) == 1 else grads
+
     # ------------------------------------------------------------------
+    def _adjoint_native(self, grads):
+        from .._backend import rccl
+
+        comm_id = rccl._handle(self.comm) if self._has_remote else -1
+        rccl.ext().halo_adjoint_nd(
+            list(grads), self.levels, self.ny, self.nx, self.width,
+            self._send_to, self._recv_from, self._local_mask,
+            self._sbuf, self._rbuf, comm_id)
+
+    def _adjoint_py(self, grads):
+        from ..ops.sendrecv import sendrecv
+        from ..ops.send import send
+        from ..ops.recv import recv
+
+        L, ny, nx, nf = self.levels, self.ny, self.nx, self.nfields
+        w = self.width
+        views = [g.view(L, ny, nx) for g in grads]
+        ents = self._entries
+
+        def slot(buf, e):
+            return buf[e["off"]:e["off"] + e["n"]].view(
+                nf, L, e["h"], e["wd"])
+
+        # adjoint pack: receive windows, read before anything is written.
+        # The corner rows of a column slot that a corner entry owned in
+        # the forward pass were never written from this slot: zeros.
+        for e in ents:
+            if e["recv_from"] is None:
+                continue
+            y0, x0 = e["recv"]
+            dst = slot(self._rbuf if e["local"] else self._sbuf, e)
+            for k, v in enumerate(views):
+                dst[k].copy_(v[:, y0:y0 + e["h"], x0:x0 + e["wd"]])
+            if e["index"] < 2:
+                lo, hi = (6, 4) if e["index"] == 0 else (7, 5)
+                if ents[lo]["recv_from"] is not None:
+                    dst[:, :, :w].zero_()
+                if ents[hi]["recv_from"] is not None:
+                    dst[:, :, e["h"] - w:].zero_()
+
+        # one message per direction, fixed order, roles swapped
+        me = self.comm.rank
+        for e in ents:
+            st, rf = e["recv_from"], e["send_to"]
+            if e["local"] or (st is None and rf is None):
+                continue
+            sview = slot(self._sbuf, e)
+            rview = slot(self._rbuf, e)
+            if st == me and rf == me:
+                rview.copy_(sview)
+            elif st is None:
+                rview.copy_(recv(rview, source=rf, comm=self.comm))
+            elif rf is None:
+                send(sview, dest=st, comm=self.comm)
+            else:
+                rview.copy_(sendrecv(sview, rview, source=rf, dest=st,
+                                     comm=self.comm))
+
+        # accumulate: own value (0 where the forward pass overwrote the
+        # cell), then the received terms in REVERSE entry order; the half
+        # types sum on a float32 copy and round once
+        half = self.dtype in (torch.float16, torch.bfloat16)
+        acc = [v.float() for v in views] if half else views
+        for e in ents:
+            if e["recv_from"] is None:
+                continue
+            y0, x0 = e["recv"]
+            for a in acc:
+                a[:, y0:y0 + e["h"], x0:x0 + e["wd"]].zero_()
+        for e in reversed(ents):
+            if e["send_to"] is None:
+                continue
+            y0, x0 = e["send"]
+            src = slot(self._rbuf, e)
+            for k, a in enumerate(acc):
+                a[:, y0:y0 + e["h"], x0:x0 + e["wd"]] += (
+                    src[k].float() if half else src[k])
+        if half:
+            for v, a in zip(views, acc):
+                v.copy_(a)
+
     def _exchange_native(self, fields):
         from .._backend import rccl
 
@@ -289,3 +476,27 @@ class HaloExchanger:
             src = slot(self._rbuf, e)
             for k, v in enumerate(views):
                 v[:, y0:y0 + e["h"], x0:x0 + e["wd"]].copy_(src[k])
+
+
+class _ExchangeAD(torch.autograd.Function):
+    """``HaloExchanger.exchange_ad``: forward = ``exchange_`` on clones,
+    backward = ``adjoint_`` on contiguous clones of the gradients."""
+
+    @staticmethod
+    def forward(ctx, ex, *fields):
+        ctx.ex = ex
+        out = tuple(f.detach().clone() for f in fields)
+        ex.exchange_(*out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        # gradients of unused outputs arrive materialised as zeros; every
+        # rank runs the same collective whatever its loss looks at
+        gin = tuple(g.detach().clone(memory_format=torch.contiguous_format)
+                    for g in grads)
+        ctx.ex.adjoint_(*gin)
+        return (None,) + tuple(
+            g if need else None
+            for g, need in zip(gin, ctx.needs_input_grad[1:]))

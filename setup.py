@@ -82,7 +82,7 @@ def build_native(force=False, variant=""):
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
-        deps = [sp, CSRC / "kernels.h"]
+        deps = [sp, CSRC / "kernels.h", CSRC / "halo_geom.h"]
         variant_flags = []
         if variant == "nofma" and src.endswith(".hip"):
             variant_flags = ["-ffp-contract=off"]
