@@ -1025,18 +1025,40 @@ HaloNdPlan halo_nd_plan(const char* who,
 // local_mask marks a self-peer entry: it is packed straight into slot i
 // of the RECEIVE buffer and never enters the group.  Messages travel as
 // raw bytes, so any dtype of a supported element size is exchanged.
-void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
-                      int64_t ny, int64_t nx, int64_t width,
-                      std::vector<int64_t> send_to,
-                      std::vector<int64_t> recv_from, int64_t local_mask,
-                      at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
-  ROCTX_SCOPE("mpi4jax_amd::halo_exchange_nd");
-  const HaloNdPlan plan =
-      halo_nd_plan("halo_exchange_nd", fields, levels, ny, nx, width,
-                   send_to, recv_from, local_mask, sbuf, rbuf);
+//
+// halo_exchange_send is the part halo_stencil_nd shares: the pack launch
+// and the RCCL group.  The caller enqueues what consumes the receive slots
+// (halo_exchange_nd its unpack launch, built here as `un`; halo_stencil_nd
+// its own kernel) and arms the watchdog when `rank` >= 0.
+
+// The communicator of a call with a remote entry, its peers checked
+// against the communicator's size.  False when nothing is remote.
+bool halo_peers(const HaloNdPlan& plan, int64_t comm_id,
+                const std::vector<int64_t>& send_to,
+                const std::vector<int64_t>& recv_from, CommEntry* c) {
+  if (!plan.any_remote) return false;
+  *c = get_comm(comm_id);
+  for (int i = 0; i < kHaloDirs; ++i) {
+    TORCH_CHECK(send_to[i] < c->size && recv_from[i] < c->size,
+                "halo peer out of range for communicator of size ", c->size);
+  }
+  return true;
+}
+
+struct HaloNdSent {
+  HaloNdArgs un;  // the unpack launch of this exchange
+  hipStream_t stream;
+  int rank;  // of this process in the group's communicator; -1: no group
+};
+
+HaloNdSent halo_exchange_send(const char* log_name, const HaloNdPlan& plan,
+                              int64_t levels, int64_t ny, int64_t nx,
+                              const std::vector<int64_t>& send_to,
+                              const std::vector<int64_t>& recv_from,
+                              int64_t local_mask, const at::Tensor& sbuf,
+                              const at::Tensor& rbuf, int64_t comm_id) {
   const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
   const int64_t total = plan.total;
-  const bool any_remote = plan.any_remote;
   const int64_t* slot_off = plan.g.slot_off;
   const int64_t *sy = plan.g.sy, *sx = plan.g.sx, *ry = plan.g.ry,
                 *rx = plan.g.rx, *hh = plan.g.hh, *ww = plan.g.ww;
@@ -1091,17 +1113,12 @@ void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
   for (int i = npk; i < kHaloDirs; ++i) pk.seg[i].end = pk.total;
   for (int i = nun; i < kHaloDirs; ++i) un.seg[i].end = un.total;
 
+  CommEntry c{};
+  const bool remote = halo_peers(plan, comm_id, send_to, recv_from, &c);
   hipStream_t stream = cur_stream();
   launch_halo_nd(pk, 0, (int)esz, stream);
-
-  if (any_remote) {
-    auto c = get_comm(comm_id);
-    for (int i = 0; i < kHaloDirs; ++i) {
-      TORCH_CHECK(send_to[i] < c.size && recv_from[i] < c.size,
-                  "halo peer out of range for communicator of size ",
-                  c.size);
-    }
-    log_enqueue("HaloExchangeNd", c, total);
+  if (remote) {
+    log_enqueue(log_name, c, total);
     RCCL_CHECK(ncclGroupStart());
     for (int i = 0; i < kHaloDirs; ++i) {
       if (is_local(i)) continue;
@@ -1116,11 +1133,45 @@ void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
       }
     }
     RCCL_CHECK(ncclGroupEnd());
-    launch_halo_nd(un, 1, (int)esz, stream);
-    watchdog_arm("halo_exchange_nd", c.rank, stream);
-  } else {
-    launch_halo_nd(un, 1, (int)esz, stream);
   }
+  return HaloNdSent{un, stream, remote ? c.rank : -1};
+}
+
+void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
+                      int64_t ny, int64_t nx, int64_t width,
+                      std::vector<int64_t> send_to,
+                      std::vector<int64_t> recv_from, int64_t local_mask,
+                      at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_exchange_nd");
+  const HaloNdPlan plan =
+      halo_nd_plan("halo_exchange_nd", fields, levels, ny, nx, width,
+                   send_to, recv_from, local_mask, sbuf, rbuf);
+  const HaloNdSent sent =
+      halo_exchange_send("HaloExchangeNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  launch_halo_nd(sent.un, 1, (int)plan.esz, sent.stream);
+  if (sent.rank >= 0) watchdog_arm("halo_exchange_nd", sent.rank, sent.stream);
+}
+
+// The checks halo_adjoint_nd adds to halo_nd_plan's, shared with
+// halo_stencil_adjoint_nd, which must pass them before its first launch.
+HaloFrame halo_adjoint_checks(const HaloNdPlan& plan,
+                              const std::vector<at::Tensor>& fields,
+                              int64_t levels, int64_t ny, int64_t nx,
+                              const at::Tensor& sbuf,
+                              const at::Tensor& rbuf) {
+  const auto st = fields[0].scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
+                  st == at::kBFloat16,
+              "halo adjoint supports float16, bfloat16, float32 and "
+              "float64, got ", st);
+  TORCH_CHECK(sbuf.scalar_type() == st && rbuf.scalar_type() == st,
+              "halo adjoint staging buffers must have the fields' dtype");
+  const HaloFrame fr = halo_frame(ny, nx, plan.w);
+  const int64_t work = plan.nf * levels * fr.per_level;
+  TORCH_CHECK_VALUE(work < ((int64_t)1 << 31), "halo adjoint over ", work,
+                    " frame cells exceeds the 2^31 work-item limit");
+  return fr;
 }
 
 // Adjoint of halo_exchange_nd, in place on the gradients `fields`; same
@@ -1151,17 +1202,9 @@ void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
                    send_to, recv_from, local_mask, sbuf, rbuf);
   const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
   const HaloGeom& g = plan.g;
-  const auto st = fields[0].scalar_type();
-  TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
-                  st == at::kBFloat16,
-              "halo adjoint supports float16, bfloat16, float32 and "
-              "float64, got ", st);
-  TORCH_CHECK(sbuf.scalar_type() == st && rbuf.scalar_type() == st,
-              "halo adjoint staging buffers must have the fields' dtype");
-  const HaloFrame fr = halo_frame(ny, nx, w);
+  const HaloFrame fr =
+      halo_adjoint_checks(plan, fields, levels, ny, nx, sbuf, rbuf);
   const int64_t work = nf * levels * fr.per_level;
-  TORCH_CHECK_VALUE(work < ((int64_t)1 << 31), "halo adjoint over ", work,
-                    " frame cells exceeds the 2^31 work-item limit");
   auto is_local = [&](int i) { return (local_mask >> i) & 1; };
 
   char* sb = (char*)sbuf.data_ptr();
@@ -1213,16 +1256,12 @@ void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
   ac.per_level = (unsigned)fr.per_level;
   ac.total = (unsigned)work;
 
+  CommEntry c{};
+  const bool remote = halo_peers(plan, comm_id, send_to, recv_from, &c);
   hipStream_t stream = cur_stream();
   launch_halo_nd(pk, 2, (int)esz, stream);
 
-  if (plan.any_remote) {
-    auto c = get_comm(comm_id);
-    for (int i = 0; i < kHaloDirs; ++i) {
-      TORCH_CHECK(send_to[i] < c.size && recv_from[i] < c.size,
-                  "halo peer out of range for communicator of size ",
-                  c.size);
-    }
+  if (remote) {
     log_enqueue("HaloAdjointNd", c, plan.total);
     RCCL_CHECK(ncclGroupStart());
     for (int i = 0; i < kHaloDirs; ++i) {
@@ -1243,6 +1282,205 @@ void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
   } else {
     launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
   }
+}
+
+// ---- fused halo stencil (parallel/stencil.HaloStencil, stencil.hip)
+
+// Checks of both stencil entries beyond halo_nd_plan's on `fields`, and
+// the kernel arguments that do not depend on the mode.  Raises before
+// anything is enqueued.
+HaloStencilArgs halo_stencil_args(const char* who, const HaloNdPlan& plan,
+                                  const std::vector<at::Tensor>& fields,
+                                  const std::vector<at::Tensor>& outs,
+                                  int64_t levels, int64_t ny, int64_t nx,
+                                  const std::vector<int64_t>& tap_dy,
+                                  const std::vector<int64_t>& tap_dx,
+                                  const std::vector<double>& tap_coef,
+                                  bool transposed, unsigned* blocks) {
+  const int64_t nf = plan.nf, w = plan.w;
+  TORCH_CHECK(w <= kStencilMaxWidth, who, ": stencil width ", w,
+              " exceeds ", kStencilMaxWidth);
+  const size_t nt = tap_dy.size();
+  TORCH_CHECK(nt >= 1 && nt <= (size_t)kStencilMaxTaps &&
+                  tap_dx.size() == nt && tap_coef.size() == nt,
+              who, ": the three tap lists must have one length in 1..",
+              kStencilMaxTaps);
+  for (size_t t = 0; t < nt; ++t) {
+    TORCH_CHECK(-w <= tap_dy[t] && tap_dy[t] <= w && -w <= tap_dx[t] &&
+                    tap_dx[t] <= w,
+                who, ": tap ", t, " reaches past the halo width ", w);
+  }
+  const at::Tensor& f0 = fields[0];
+  const auto st = f0.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
+                  st == at::kBFloat16,
+              who, " supports float16, bfloat16, float32 and float64, got ",
+              st);
+  TORCH_CHECK((int64_t)outs.size() == nf, who, ": ", nf, " field(s) but ",
+              outs.size(), " output(s)");
+  for (int64_t k = 0; k < nf; ++k) {
+    const auto& o = outs[k];
+    TORCH_CHECK(o.is_cuda() && o.is_contiguous() &&
+                    o.sizes() == fields[k].sizes() &&
+                    o.scalar_type() == st && o.device() == f0.device(),
+                who, ": bad output ", k);
+  }
+  // address ranges: an output overlaps neither an input nor another output
+  const int64_t bytes = f0.numel() * plan.esz;
+  for (int64_t k = 0; k < nf; ++k) {
+    const char* o = (const char*)outs[k].data_ptr();
+    for (int64_t j = 0; j < nf; ++j) {
+      const char* i = (const char*)fields[j].data_ptr();
+      TORCH_CHECK_VALUE(o + bytes <= i || i + bytes <= o, who, ": output ",
+                        k, " overlaps input ", j);
+      if (j < k) {
+        const char* p = (const char*)outs[j].data_ptr();
+        TORCH_CHECK_VALUE(o + bytes <= p || p + bytes <= o, who,
+                          ": output ", k, " overlaps output ", j);
+      }
+    }
+  }
+  const int64_t org = transposed ? 0 : w;
+  const int64_t tiles_y = (ny - 2 * org + kStencilTileY - 1) / kStencilTileY;
+  const int64_t tiles_x = (nx - 2 * org + kStencilTileX - 1) / kStencilTileX;
+  // HIP refuses a launch of 2^32 threads or more: 256-thread blocks, so
+  // fewer than 2^24 of them
+  const int64_t planes = nf * levels;  // < 2^34
+  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
+  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
+                        planes * (tiles_y * tiles_x) < max_blocks,
+                    who, ": ", planes, " planes of ", tiles_y, " x ", tiles_x,
+                    " tiles exceed the launch limit of 2^24 blocks");
+  *blocks = (unsigned)(planes * tiles_y * tiles_x);
+
+  HaloStencilArgs a{};
+  for (int64_t k = 0; k < nf; ++k) {
+    a.in[k] = fields[k].data_ptr();
+    a.out[k] = outs[k].data_ptr();
+  }
+  const int64_t stride = kStencilTileX + 2 * w;
+  for (size_t t = 0; t < nt; ++t) {
+    if (st == at::kDouble) {
+      a.coef.f64[t] = tap_coef[t];
+    } else {
+      a.coef.f32[t] = (float)tap_coef[t];
+    }
+    const int64_t off = tap_dy[t] * stride + tap_dx[t];
+    a.tap_off[t] = (int)(transposed ? -off : off);
+  }
+  a.ny = ny;
+  a.nx = nx;
+  a.levels = (unsigned)levels;
+  a.tiles_y = (unsigned)tiles_y;
+  a.tiles_x = (unsigned)tiles_x;
+  a.w = (int)w;
+  a.ntaps = (int)nt;
+  return a;
+}
+
+// Native executor of HaloStencil.apply: outs = P_int . S . E (fields),
+// the fields themselves never written.  Arguments as halo_exchange_nd,
+// plus the outputs and the taps (dy, dx, coefficient) in the order they
+// are added.
+//
+// Where the exchange would have written halo cell (y, x) from, by region
+// (low halo, interior, high halo) along y and x: a side region from its
+// column or row entry, a corner region from its corner entry or else from
+// the column entry on its side ("corners win"), and from itself when that
+// entry has no sender.
+//   * No remote entry (direct path): ONE launch.  A received cell is read
+//     from the input field at the entry's send window, so the staging
+//     buffers are not touched and no communicator is looked up.
+//   * Otherwise (staged path): halo_exchange_nd's pack launch and RCCL
+//     group, then ONE stencil launch that reads received cells from the
+//     receive slots instead of unpacking them.
+void halo_stencil_nd(std::vector<at::Tensor> fields,
+                     std::vector<at::Tensor> outs, int64_t levels,
+                     int64_t ny, int64_t nx, int64_t width,
+                     std::vector<int64_t> tap_dy,
+                     std::vector<int64_t> tap_dx,
+                     std::vector<double> tap_coef,
+                     std::vector<int64_t> send_to,
+                     std::vector<int64_t> recv_from, int64_t local_mask,
+                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil_nd");
+  const char* who = "halo_stencil_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  HaloStencilArgs a =
+      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, false, &blocks);
+  const HaloGeom& g = plan.g;
+  const char* rb = (const char*)rbuf.data_ptr();
+  // entry of region [ky][kx]; for a corner, the corner entry and then the
+  // column entry that covers it
+  static const int first[9] = {7, 2, 6, 1, -1, 0, 5, 3, 4};
+  static const int second[9] = {1, -1, 0, -1, -1, -1, 1, -1, 0};
+  for (int k = 0; k < 9; ++k) {
+    StencilRegion& r = a.reg[k];
+    r.kind = STENCIL_OWN;
+    int e = first[k];
+    if (e >= 0 && recv_from[e] < 0) e = second[k];
+    if (e < 0 || recv_from[e] < 0) continue;
+    if (plan.any_remote) {
+      r.kind = STENCIL_SLOT;
+      r.buf = rb + g.slot_off[e] * plan.esz;
+      r.ry = (int)g.ry[e];
+      r.rx = (int)g.rx[e];
+      r.h = (unsigned)g.hh[e];
+      r.wd = (unsigned)g.ww[e];
+    } else {
+      r.kind = STENCIL_OFFSET;
+      r.shift = (g.sy[e] - g.ry[e]) * nx + (g.sx[e] - g.rx[e]);
+    }
+  }
+
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    HIP_CHECK(launch_halo_stencil(a, 0, dt, blocks, cur_stream()));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloStencilNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_stencil(a, 0, dt, blocks, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// Native executor of HaloStencil.adjoint: gins = E^T . S^T . P_int (gouts).
+// One launch of the stencil kernel's transposed mode writes every cell of
+// `gins`; halo_adjoint_nd then runs in place on them.
+void halo_stencil_adjoint_nd(std::vector<at::Tensor> gouts,
+                             std::vector<at::Tensor> gins, int64_t levels,
+                             int64_t ny, int64_t nx, int64_t width,
+                             std::vector<int64_t> tap_dy,
+                             std::vector<int64_t> tap_dx,
+                             std::vector<double> tap_coef,
+                             std::vector<int64_t> send_to,
+                             std::vector<int64_t> recv_from,
+                             int64_t local_mask, at::Tensor sbuf,
+                             at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil_adjoint_nd");
+  const char* who = "halo_stencil_adjoint_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  const HaloStencilArgs a =
+      halo_stencil_args(who, plan, gouts, gins, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, true, &blocks);
+  // everything halo_adjoint_nd will ask of `gins`, before the launch
+  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
+  CommEntry c{};  // looked up only to be checked before the launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  HIP_CHECK(launch_halo_stencil(a, 1, dt_code(gouts[0]), blocks,
+                                cur_stream()));
+  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
+                  std::move(recv_from), local_mask, std::move(sbuf),
+                  std::move(rbuf), comm_id);
 }
 
 // direct access to the combine kernel (used by gpu numerics tests)
@@ -1302,4 +1540,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("unpack_halo", &unpack_halo);
   m.def("halo_exchange_nd", &halo_exchange_nd);
   m.def("halo_adjoint_nd", &halo_adjoint_nd);
+  m.def("halo_stencil_nd", &halo_stencil_nd);
+  m.def("halo_stencil_adjoint_nd", &halo_stencil_adjoint_nd);
 }

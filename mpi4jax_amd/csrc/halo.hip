@@ -25,6 +25,7 @@
 // up to 9 terms and the work item is the field cell, which gathers them —
 // no atomics, no race, a fixed order of adds.
 
+#include "halo_types.h"
 #include "kernels.h"
 
 #include <cstdint>
@@ -88,35 +89,8 @@ void launch_t(const HaloNdArgs& a, int unpack, hipStream_t stream) {
   }
 }
 
-// ---- adjoint accumulate: typed, one work item per frame cell
-
-struct Bf16 {
-  uint16_t bits;
-};
-
-template <typename T, typename Acc>
-__device__ inline Acc adj_load(const T* p) {
-  return (Acc)*p;
-}
-template <>
-__device__ inline float adj_load<Bf16, float>(const Bf16* p) {
-  return __uint_as_float((uint32_t)p->bits << 16);
-}
-
-template <typename T, typename Acc>
-__device__ inline void adj_store(T* p, Acc v) {
-  *p = (T)v;  // float -> _Float16 rounds to nearest even
-}
-template <>
-__device__ inline void adj_store<Bf16, float>(Bf16* p, float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) {
-    p->bits = 0x7fc0;  // NaN
-  } else {
-    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even
-    p->bits = (uint16_t)(u >> 16);
-  }
-}
+// ---- adjoint accumulate: typed (halo_types.h), one work item per frame
+// cell
 
 template <typename T, typename Acc>
 __global__ __launch_bounds__(kHaloBlock) void halo_adjoint_acc_kernel(

@@ -203,3 +203,63 @@ struct HaloAdjArgs {
 // dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16.
 void launch_halo_adjoint_acc(const HaloAdjArgs& a, int dt_code,
                              hipStream_t stream);
+
+// Fused halo stencil of parallel/stencil.HaloStencil (stencil.hip).  One
+// launch covers every (ny, nx) plane of every field.  A workgroup owns a
+// kStencilTileY x kStencilTileX tile of output cells of one plane: it
+// fills an LDS tile with a `w`-cell apron, converted to the accumulate
+// type (float32 for f16 / bf16 / f32, float64 for f64), then every thread
+// sums the taps, in the order given and from 0, for its outputs.
+//
+// mode 0 (apply): the outputs are the interior cells; an input cell of the
+// halo is read through the 3 x 3 region table, indexed
+// [low halo, interior, high halo] along y times the same along x: the
+// cell's own value, the input field at an offset (a local periodic wrap),
+// or a receive staging slot laid out [field][level][row][col].  Only the
+// interior of `out` is written.
+// mode 1 (transposed): the outputs are all cells; an input cell counts
+// only where it is interior and reads as 0 elsewhere; the region table is
+// not used.  `tap_off` then carries the negated offsets.
+//
+// Block index, plane index and tile indices are 32-bit.  A launch holds
+// fewer than 2^32 threads, so the caller checks blocks < 2^32 /
+// kStencilBlock = 2^24; offsets into a field or a slot are 64-bit.
+constexpr int kStencilMaxTaps = 81;
+constexpr int kStencilMaxWidth = 4;
+constexpr int kStencilTileX = 64;
+constexpr int kStencilTileY = 32;
+constexpr int kStencilBlock = 256;  // threads per block
+
+enum StencilSource : int {
+  STENCIL_OWN = 0,     // the cell itself
+  STENCIL_OFFSET = 1,  // the input field at (y + dj, x + di)
+  STENCIL_SLOT = 2,    // staging slot element (y - ry, x - rx)
+};
+
+struct StencilRegion {
+  const void* buf;  // STENCIL_SLOT: the slot
+  long long shift;  // STENCIL_OFFSET: dj * nx + di
+  int kind;
+  int ry, rx;       // STENCIL_SLOT: origin of the slot's window
+  unsigned h, wd;   // STENCIL_SLOT: extent of the slot's window
+};
+
+struct HaloStencilArgs {
+  const void* in[kHaloMaxFields];
+  void* out[kHaloMaxFields];
+  StencilRegion reg[9];
+  union {  // coefficients in the accumulate type
+    double f64[kStencilMaxTaps];
+    float f32[kStencilMaxTaps];
+  } coef;
+  int tap_off[kStencilMaxTaps];  // dy * (kStencilTileX + 2 * w) + dx
+  long long ny, nx;
+  unsigned levels, tiles_y, tiles_x;
+  int w, ntaps;
+};
+
+// dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16; `blocks` is
+// nf * levels * tiles_y * tiles_x.  Returns the launch's status.
+hipError_t launch_halo_stencil(const HaloStencilArgs& a, int mode,
+                               int dt_code, unsigned blocks,
+                               hipStream_t stream);

@@ -10,6 +10,8 @@ from .comm import (  # noqa: F401
 from .grid import CartesianGrid  # noqa: F401
 from .halo import HaloExchanger  # noqa: F401
 from . import halo  # noqa: F401
+from .stencil import HaloStencil  # noqa: F401
+from . import stencil  # noqa: F401
 from .ddp import average_gradients  # noqa: F401
 from .tp import (  # noqa: F401
     ColumnParallelLinear,

@@ -179,6 +179,20 @@ class CartesianGrid:
         return HaloExchanger(self, shape, dtype, device, width=width,
                              nfields=nfields, _force_remote=_force_remote)
 
+    def make_stencil(self, shape, dtype, device, weights, nfields=1,
+                     _force_remote=False):
+        """Build a :class:`~.stencil.HaloStencil`: the constant-coefficient
+        stencil ``weights`` — a ``(2r+1, 2r+1)`` table, ``1 <= r <= 4``,
+        entry ``[a][b]`` multiplying the cell at offset ``(a-r, b-r)`` in
+        ``(y, x)`` — applied through a halo exchange of width ``r`` as one
+        operator with a native adjoint.  ``shape``, ``nfields`` and
+        ``_force_remote`` are those of :meth:`make_halo_exchanger`.
+        """
+        from .stencil import HaloStencil
+
+        return HaloStencil(self, shape, dtype, device, weights,
+                           nfields=nfields, _force_remote=_force_remote)
+
     def _halo_exchange_impl(self, out):
         # imported here to avoid a circular import at package init
         from ..ops.sendrecv import sendrecv
