@@ -57,7 +57,11 @@ __host__ __device__ inline int xcd_band_id(B b, int T) {
   const int j = id_ / gx_;                                                 \
   const int i = (id_ % gx_) * kBlock + (int)threadIdx.x
 
-constexpr float G = 9.81f;
+// gravity (the model's GRAVITY).  The templated scalar stages convert the
+// double to their own type: a float64 kernel must not compute with the
+// float32 rounding of 9.81 (relative error 4e-8 in the pressure gradient).
+constexpr double kGravity = 9.81;
+constexpr float G = 9.81f;  // == (float)kGravity, float-only kernels
 
 struct SwFlags {
   // "open" = this halo receives neighbor data (exchange or periodic wrap)
@@ -289,7 +293,7 @@ __device__ inline CellUpd<T> stage8_math(const SwArgs<T>& a, int j, int i) {
   T qc = q_at(a, j, i), qs = q_at(a, j - 1, i), qw = q_at(a, j, i - 1);
   T fnc = fn_at(a, j, i), fne = fn_at(a, j, i + 1);
   T fns = fn_at(a, j - 1, i), fnse = fn_at(a, j - 1, i + 1);
-  T dnu = -G * (a.h[idx + 1] - h_) / a.dx +
+  T dnu = -T(kGravity) * (a.h[idx + 1] - h_) / a.dx +
           T(0.5) * (qc * T(0.5) * (fnc + fne) +
                     qs * T(0.5) * (fns + fnse));
   dnu -= (ke_at(a, j, i + 1) - ke_at(a, j, i)) / a.dx;
@@ -297,7 +301,7 @@ __device__ inline CellUpd<T> stage8_math(const SwArgs<T>& a, int j, int i) {
 
   T fec = fe_at(a, j, i), fen = fe_at(a, j + 1, i);
   T few = fe_at(a, j, i - 1), fenw = fe_at(a, j + 1, i - 1);
-  T dnv = -G * (a.h[idx + nx] - h_) / a.dy -
+  T dnv = -T(kGravity) * (a.h[idx + nx] - h_) / a.dy -
           T(0.5) * (qc * T(0.5) * (fec + fen) +
                     qw * T(0.5) * (few + fenw));
   dnv -= (ke_at(a, j + 1, i) - ke_at(a, j, i)) / a.dy;
@@ -362,14 +366,14 @@ __device__ inline void stage6_cell(const SwArgs<T>& a, int j, int i) {
           (a.fn[idx] - a.fn[idx - nx]) / a.dy;
   a.dnh[idx] = dnh;
 
-  T dnu = -G * (a.h[idx + 1] - h_) / a.dx +
+  T dnu = -T(kGravity) * (a.h[idx + 1] - h_) / a.dx +
           T(0.5) * (a.q[idx] * T(0.5) * (a.fn[idx] + a.fn[idx + 1]) +
                     a.q[idx - nx] * T(0.5) *
                         (a.fn[idx - nx] + a.fn[idx - nx + 1]));
   dnu -= (a.ke[idx + 1] - a.ke[idx]) / a.dx;
   a.dnu[idx] = dnu;
 
-  T dnv = -G * (a.h[idx + nx] - h_) / a.dy -
+  T dnv = -T(kGravity) * (a.h[idx + nx] - h_) / a.dy -
           T(0.5) * (a.q[idx] * T(0.5) * (a.fe[idx] + a.fe[idx + nx]) +
                     a.q[idx - 1] * T(0.5) *
                         (a.fe[idx - 1] + a.fe[idx + nx - 1]));

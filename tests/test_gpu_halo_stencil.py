@@ -28,9 +28,30 @@ pytestmark = pytest.mark.gpu
 ALL = OPEN + [(False, False)]
 DTYPES = (torch.float32, torch.float64, torch.bfloat16, torch.float16)
 # several tiles in both axes plus a ragged edge (tiles are 32 x 64)
-BIG = [(3, 41, 70), (2, 67, 131)]
-# n == 3 * width and 3 * width + 1 at width 4, and the larger of BIG
-MORE = [(12, 12), (13, 12), (2, 67, 131)]
+BIG = [(3, 41, 70), (2, 67, 131), (2, 76, 140)]
+# n == 3 * width and 3 * width + 1 at width 4, and the larger two of BIG:
+# (2, 67, 131) has a tile on the kernel's fast fill at width 1 only,
+# (2, 76, 140) one at every width in both modes (test_fast_fill_is_reached)
+MORE = [(12, 12), (13, 12), (2, 67, 131), (2, 76, 140)]
+TILE_Y, TILE_X = 32, 64  # kStencilTileY, kStencilTileX of csrc/kernels.h
+
+
+def fast_tiles(ny, nx, w, mode):
+    """Tiles of an (ny, nx) plane that take halo_stencil_kernel's fast
+    fill (the register-staged main[]/side[] loads): its `fast` condition,
+    evaluated for every tile of the launch.  mode 0 = apply (outputs are
+    the interior), 1 = adjoint (the full array)."""
+    org = w if mode == 0 else 0
+    oy, ox = (ny - 2 * w, nx - 2 * w) if mode == 0 else (ny, nx)
+    rows, stride = TILE_Y + 2 * w, TILE_X + 2 * w
+    n = 0
+    for tiy in range(-(-oy // TILE_Y)):
+        for tix in range(-(-ox // TILE_X)):
+            fy0 = org + tiy * TILE_Y - w
+            fx0 = org + tix * TILE_X - w
+            n += (fy0 >= w and fx0 >= w and fy0 + rows <= ny - w
+                  and fx0 + stride <= nx - w)
+    return n
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -53,6 +74,17 @@ def _ext():
 
 def _cuda(ts):
     return [t.cuda() for t in ts]
+
+
+def test_fast_fill_is_reached():
+    """The shapes of MORE put at least one tile on the fast fill at every
+    width in both modes (so the ten fill iterations of width 4 run), and
+    the previous largest shape did so at width 1 only."""
+    for w in (1, 2, 3, 4):
+        for mode in (0, 1):
+            assert fast_tiles(76, 140, w, mode) >= 1, (w, mode)
+            assert (fast_tiles(67, 131, w, mode) >= 1) == (w == 1)
+            assert (2, 76, 140) in MORE and _valid((2, 76, 140), w)
 
 
 # ------------------------------------------------------------ direct path
@@ -86,7 +118,7 @@ def test_direct_path_matches_cpu_and_oracle(grids, periodic, w):
                                    e.to(dtype).double()), (shape, nf, dtype)
             ran += 1
     # widths 1..4 keep 10, 9, 5 and 2 of SHAPES, and all of MORE
-    assert ran >= ({1: 10, 2: 9, 3: 5, 4: 2}[w] + 3) * 3 * 4
+    assert ran >= ({1: 10, 2: 9, 3: 5, 4: 2}[w] + 4) * 3 * 4
 
 
 @pytest.mark.parametrize("periodic", ALL)
@@ -115,7 +147,7 @@ def test_direct_adjoint_matches_cpu_and_oracle(grids, periodic, w):
                     g.double(), oracle_adjoint_chain(src, k, f, dtype)), \
                     (shape, nf, dtype)
             ran += 1
-    assert ran >= ({1: 10, 2: 9, 3: 5, 4: 2}[w] + 3) * 2 * 4
+    assert ran >= ({1: 10, 2: 9, 3: 5, 4: 2}[w] + 4) * 2 * 4
 
 
 # ------------------------------------------------------------ staged path
