@@ -8,6 +8,13 @@ products are ``allreduce(SUM)`` and the matvec gathers the full iterate
 with ``allgather`` — both enqueued on the GPU stream when run on MI355X.
 
     python -m mpi4jax_amd.run -n 4 examples/distributed_cg.py --n 4096
+
+This is the dense, generic form: an ``allgather`` matvec and a host read
+of the residual in every iteration.  For a stencil operator on a
+decomposed grid use ``HaloStencil.make_cg()`` instead
+(``examples/stencil_cg_diffusion.py``): halo exchange and matvec are one
+kernel, the vector updates are fused with the inner products, and the
+scalars stay on the device.
 """
 
 import argparse

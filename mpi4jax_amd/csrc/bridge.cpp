@@ -1394,24 +1394,11 @@ HaloStencilArgs halo_stencil_args(const char* who, const HaloNdPlan& plan,
 //   * Otherwise (staged path): halo_exchange_nd's pack launch and RCCL
 //     group, then ONE stencil launch that reads received cells from the
 //     receive slots instead of unpacking them.
-void halo_stencil_nd(std::vector<at::Tensor> fields,
-                     std::vector<at::Tensor> outs, int64_t levels,
-                     int64_t ny, int64_t nx, int64_t width,
-                     std::vector<int64_t> tap_dy,
-                     std::vector<int64_t> tap_dx,
-                     std::vector<double> tap_coef,
-                     std::vector<int64_t> send_to,
-                     std::vector<int64_t> recv_from, int64_t local_mask,
-                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
-  ROCTX_SCOPE("mpi4jax_amd::halo_stencil_nd");
-  const char* who = "halo_stencil_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
-  unsigned blocks = 0;
-  HaloStencilArgs a =
-      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, false, &blocks);
+// The region table of mode 0: where each of the nine regions of a plane
+// reads its cells from (see above).
+void halo_stencil_regions(HaloStencilArgs& a, const HaloNdPlan& plan,
+                          const std::vector<int64_t>& recv_from,
+                          const at::Tensor& rbuf, int64_t nx) {
   const HaloGeom& g = plan.g;
   const char* rb = (const char*)rbuf.data_ptr();
   // entry of region [ky][kx]; for a corner, the corner entry and then the
@@ -1436,6 +1423,27 @@ void halo_stencil_nd(std::vector<at::Tensor> fields,
       r.shift = (g.sy[e] - g.ry[e]) * nx + (g.sx[e] - g.rx[e]);
     }
   }
+}
+
+void halo_stencil_nd(std::vector<at::Tensor> fields,
+                     std::vector<at::Tensor> outs, int64_t levels,
+                     int64_t ny, int64_t nx, int64_t width,
+                     std::vector<int64_t> tap_dy,
+                     std::vector<int64_t> tap_dx,
+                     std::vector<double> tap_coef,
+                     std::vector<int64_t> send_to,
+                     std::vector<int64_t> recv_from, int64_t local_mask,
+                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil_nd");
+  const char* who = "halo_stencil_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  HaloStencilArgs a =
+      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, false, &blocks);
+  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
 
   const int dt = dt_code(fields[0]);
   if (!plan.any_remote) {
@@ -1447,6 +1455,273 @@ void halo_stencil_nd(std::vector<at::Tensor> fields,
                          recv_from, local_mask, sbuf, rbuf, comm_id);
   HIP_CHECK(launch_halo_stencil(a, 0, dt, blocks, sent.stream));
   watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// ---- Krylov layer over the stencil (parallel/cg.StencilCG, krylov.hip)
+
+// A float64 device scalar (0-d or one element) on `dev`.
+double* krylov_scalar(const char* who, const char* name,
+                      const at::Tensor& t, const at::Device& dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev &&
+                  t.scalar_type() == at::kDouble && t.numel() == 1 &&
+                  t.dim() <= 1,
+              who, ": ", name,
+              " must be a float64 0-d or one-element tensor on the fields' "
+              "device");
+  return (double*)t.data_ptr();
+}
+
+// The partials buffer: float64, contiguous, on `dev`, one slot per block.
+double* krylov_partials(const char* who, const at::Tensor& t,
+                        const at::Device& dev, unsigned blocks) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev &&
+                  t.scalar_type() == at::kDouble && t.is_contiguous() &&
+                  t.numel() >= (int64_t)blocks,
+              who, ": partials must be a contiguous float64 tensor of at "
+              "least ", blocks, " elements on the fields' device");
+  return (double*)t.data_ptr();
+}
+
+// Neither scalar nor partials may lie inside a field that is written.
+void krylov_no_overlap(const char* who, const at::Tensor& small,
+                       const char* name,
+                       const std::vector<at::Tensor>& written) {
+  const char* lo = (const char*)small.data_ptr();
+  const char* hi = lo + small.numel() * small.element_size();
+  for (size_t k = 0; k < written.size(); ++k) {
+    const char* f = (const char*)written[k].data_ptr();
+    const char* fe = f + written[k].numel() * written[k].element_size();
+    TORCH_CHECK_VALUE(hi <= f || fe <= lo, who, ": ", name,
+                      " overlaps written field ", k);
+  }
+}
+
+// Geometry and field checks of the elementwise Krylov entries; `lists`
+// are the field lists, all of one length, shape, dtype and device.
+KrylovArgs krylov_args(const char* who,
+                       const std::vector<const std::vector<at::Tensor>*>&
+                           lists,
+                       int64_t levels, int64_t ny, int64_t nx, int64_t w,
+                       bool cg, unsigned* blocks) {
+  const int64_t nf = (int64_t)lists[0]->size();
+  TORCH_CHECK(1 <= nf && nf <= kHaloMaxFields, who, ": 1..", kHaloMaxFields,
+              " fields supported, got ", nf);
+  TORCH_CHECK(w >= 1 && w <= kStencilMaxWidth && levels >= 1 &&
+                  ny >= 3 * w && nx >= 3 * w,
+              who, ": bad geometry: levels ", levels, ", ny ", ny, ", nx ",
+              nx, ", width ", w, " (width in 1..", kStencilMaxWidth,
+              ", each axis n >= 3*width)");
+  TORCH_CHECK(levels < ((int64_t)1 << 31) && ny < ((int64_t)1 << 31) &&
+                  nx < ((int64_t)1 << 31),
+              who, ": extents must be below 2^31");
+  const at::Tensor& f0 = (*lists[0])[0];
+  const auto st = f0.scalar_type();
+  if (cg) {
+    TORCH_CHECK(st == at::kFloat || st == at::kDouble, who,
+                " supports float32 and float64, got ", st);
+  } else {
+    TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
+                    st == at::kBFloat16,
+                who, " supports float16, bfloat16, float32 and float64, "
+                "got ", st);
+  }
+  TORCH_CHECK(f0.is_cuda(), who, ": fields must live on the GPU");
+  TORCH_CHECK(levels <= f0.numel() && f0.numel() % levels == 0 &&
+                  f0.numel() / levels == ny * nx,
+              who, ": field has ", f0.numel(), " elements, expected ",
+              levels, " x ", ny, " x ", nx);
+  for (size_t li = 0; li < lists.size(); ++li) {
+    TORCH_CHECK((int64_t)lists[li]->size() == nf, who, ": field list ", li,
+                " has ", lists[li]->size(), " field(s), expected ", nf);
+    for (int64_t k = 0; k < nf; ++k) {
+      const auto& f = (*lists[li])[k];
+      TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
+                      f.numel() == f0.numel() && f.scalar_type() == st &&
+                      f.device() == f0.device(),
+                  who, ": bad field ", k, " of list ", li);
+    }
+  }
+  const int64_t tiles_y = (ny - 2 * w + kStencilTileY - 1) / kStencilTileY;
+  const int64_t tiles_x = (nx - 2 * w + kStencilTileX - 1) / kStencilTileX;
+  const int64_t planes = nf * levels;
+  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
+  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
+                        planes * (tiles_y * tiles_x) < max_blocks,
+                    who, ": ", planes, " planes of ", tiles_y, " x ", tiles_x,
+                    " tiles exceed the launch limit of 2^24 blocks");
+  *blocks = (unsigned)(planes * tiles_y * tiles_x);
+  KrylovArgs a{};
+  a.ny = ny;
+  a.nx = nx;
+  a.levels = (unsigned)levels;
+  a.tiles_y = (unsigned)tiles_y;
+  a.tiles_x = (unsigned)tiles_x;
+  a.w = (int)w;
+  return a;
+}
+
+// `written` fields overlap neither each other nor a field of `read`
+// (a field may appear in several read lists: r . r is dot(r, r)).
+void krylov_fields_disjoint(const char* who,
+                            const std::vector<at::Tensor>& written,
+                            const std::vector<at::Tensor>& read) {
+  for (size_t k = 0; k < written.size(); ++k) {
+    const char* o = (const char*)written[k].data_ptr();
+    const char* oe = o + written[k].numel() * written[k].element_size();
+    for (size_t j = 0; j < read.size(); ++j) {
+      const char* i = (const char*)read[j].data_ptr();
+      const char* ie = i + read[j].numel() * read[j].element_size();
+      TORCH_CHECK_VALUE(oe <= i || ie <= o, who, ": written field ", k,
+                        " overlaps read field ", j);
+    }
+    for (size_t j = 0; j < k; ++j) {
+      const char* i = (const char*)written[j].data_ptr();
+      const char* ie = i + written[j].numel() * written[j].element_size();
+      TORCH_CHECK_VALUE(oe <= i || ie <= o, who, ": written field ", k,
+                        " overlaps written field ", j);
+    }
+  }
+}
+
+// HaloStencil.apply_dot: halo_stencil_nd with the kernel's DOT epilogue,
+// then the finish launch: result = fields . outs over the interior of
+// this rank, in float64.  Same paths, same stored outputs.
+void halo_stencil_dot_nd(std::vector<at::Tensor> fields,
+                         std::vector<at::Tensor> outs, int64_t levels,
+                         int64_t ny, int64_t nx, int64_t width,
+                         std::vector<int64_t> tap_dy,
+                         std::vector<int64_t> tap_dx,
+                         std::vector<double> tap_coef,
+                         std::vector<int64_t> send_to,
+                         std::vector<int64_t> recv_from, int64_t local_mask,
+                         at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id,
+                         at::Tensor partials, at::Tensor result) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil_dot_nd");
+  const char* who = "halo_stencil_dot_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  HaloStencilArgs a =
+      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, false, &blocks);
+  const at::Device dev = fields[0].device();
+  a.partials = krylov_partials(who, partials, dev, blocks);
+  double* res = krylov_scalar(who, "result", result, dev);
+  krylov_no_overlap(who, partials, "partials", outs);
+  krylov_no_overlap(who, result, "result", outs);
+  krylov_no_overlap(who, result, "result", {partials});
+  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
+  CommEntry c{};  // looked up only to be checked before the first launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    hipStream_t stream = cur_stream();
+    HIP_CHECK(launch_halo_stencil_dot(a, dt, blocks, stream));
+    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloStencilDotNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_stencil_dot(a, dt, blocks, sent.stream));
+  HIP_CHECK(
+      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// HaloStencil.dot: result = a . b over the interior of this rank.  a and
+// b may be the same tensors.
+void halo_interior_dot_nd(std::vector<at::Tensor> a_fields,
+                          std::vector<at::Tensor> b_fields, int64_t levels,
+                          int64_t ny, int64_t nx, int64_t width,
+                          at::Tensor partials, at::Tensor result) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_interior_dot_nd");
+  const char* who = "halo_interior_dot_nd";
+  unsigned blocks = 0;
+  KrylovArgs a = krylov_args(who, {&a_fields, &b_fields}, levels, ny, nx,
+                             width, false, &blocks);
+  const at::Device dev = a_fields[0].device();
+  a.partials = krylov_partials(who, partials, dev, blocks);
+  double* res = krylov_scalar(who, "result", result, dev);
+  krylov_no_overlap(who, result, "result", {partials});
+  for (size_t k = 0; k < a_fields.size(); ++k) {
+    a.a[k] = a_fields[k].data_ptr();
+    a.b[k] = b_fields[k].data_ptr();
+  }
+  hipStream_t stream = cur_stream();
+  HIP_CHECK(launch_krylov(a, KRYLOV_DOT, dt_code(a_fields[0]), blocks,
+                          stream));
+  HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
+}
+
+// One CG update on the interior: alpha = rs / pq (0 when pq == 0),
+// x += alpha p, r -= alpha q; then the finish launch stores the old rs in
+// rs_old and this rank's r . r, on the stored r, in rs.
+void halo_cg_update_nd(std::vector<at::Tensor> x, std::vector<at::Tensor> r,
+                       std::vector<at::Tensor> p, std::vector<at::Tensor> q,
+                       int64_t levels, int64_t ny, int64_t nx, int64_t width,
+                       at::Tensor rs, at::Tensor pq, at::Tensor rs_old,
+                       at::Tensor partials) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_cg_update_nd");
+  const char* who = "halo_cg_update_nd";
+  unsigned blocks = 0;
+  KrylovArgs a =
+      krylov_args(who, {&x, &r, &p, &q}, levels, ny, nx, width, true,
+                  &blocks);
+  const at::Device dev = x[0].device();
+  a.partials = krylov_partials(who, partials, dev, blocks);
+  a.num = krylov_scalar(who, "rs", rs, dev);
+  a.den = krylov_scalar(who, "pq", pq, dev);
+  double* old = krylov_scalar(who, "rs_old", rs_old, dev);
+  std::vector<at::Tensor> written(x), read(p);
+  written.insert(written.end(), r.begin(), r.end());
+  read.insert(read.end(), q.begin(), q.end());
+  krylov_fields_disjoint(who, written, read);
+  const at::Tensor* small[4] = {&rs, &pq, &rs_old, &partials};
+  const char* names[4] = {"rs", "pq", "rs_old", "partials"};
+  for (int i = 0; i < 4; ++i) {
+    krylov_no_overlap(who, *small[i], names[i], written);
+    for (int j = 0; j < i; ++j) {
+      krylov_no_overlap(who, *small[i], names[i], {*small[j]});
+    }
+  }
+  for (size_t k = 0; k < x.size(); ++k) {
+    a.a[k] = p[k].data_ptr();
+    a.b[k] = q[k].data_ptr();
+    a.x[k] = x[k].data_ptr();
+    a.r[k] = r[k].data_ptr();
+  }
+  hipStream_t stream = cur_stream();
+  HIP_CHECK(launch_krylov(a, KRYLOV_UPDATE, dt_code(x[0]), blocks, stream));
+  HIP_CHECK(launch_krylov_finish(a.partials, blocks, (double*)a.num, old,
+                                 stream));
+}
+
+// The CG direction on the interior: beta = rs / rs_old (0 when
+// rs_old == 0), p = r + beta p.  The halo of p is not written.
+void halo_cg_direction_nd(std::vector<at::Tensor> p,
+                          std::vector<at::Tensor> r, int64_t levels,
+                          int64_t ny, int64_t nx, int64_t width,
+                          at::Tensor rs, at::Tensor rs_old) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_cg_direction_nd");
+  const char* who = "halo_cg_direction_nd";
+  unsigned blocks = 0;
+  KrylovArgs a =
+      krylov_args(who, {&p, &r}, levels, ny, nx, width, true, &blocks);
+  const at::Device dev = p[0].device();
+  a.num = krylov_scalar(who, "rs", rs, dev);
+  a.den = krylov_scalar(who, "rs_old", rs_old, dev);
+  krylov_fields_disjoint(who, p, r);
+  krylov_no_overlap(who, rs, "rs", p);
+  krylov_no_overlap(who, rs_old, "rs_old", p);
+  for (size_t k = 0; k < p.size(); ++k) {
+    a.a[k] = r[k].data_ptr();
+    a.r[k] = p[k].data_ptr();
+  }
+  HIP_CHECK(launch_krylov(a, KRYLOV_DIRECTION, dt_code(p[0]), blocks,
+                          cur_stream()));
 }
 
 // Native executor of HaloStencil.adjoint: gins = E^T . S^T . P_int (gouts).
@@ -1542,4 +1817,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_adjoint_nd", &halo_adjoint_nd);
   m.def("halo_stencil_nd", &halo_stencil_nd);
   m.def("halo_stencil_adjoint_nd", &halo_stencil_adjoint_nd);
+  m.def("halo_stencil_dot_nd", &halo_stencil_dot_nd);
+  m.def("halo_interior_dot_nd", &halo_interior_dot_nd);
+  m.def("halo_cg_update_nd", &halo_cg_update_nd);
+  m.def("halo_cg_direction_nd", &halo_cg_direction_nd);
 }

@@ -256,6 +256,7 @@ struct HaloStencilArgs {
   long long ny, nx;
   unsigned levels, tiles_y, tiles_x;
   int w, ntaps;
+  double* partials;  // launch_halo_stencil_dot: one slot per block
 };
 
 // dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16; `blocks` is
@@ -263,3 +264,52 @@ struct HaloStencilArgs {
 hipError_t launch_halo_stencil(const HaloStencilArgs& a, int mode,
                                int dt_code, unsigned blocks,
                                hipStream_t stream);
+
+// Mode 0 of the same kernel with its DOT epilogue: block `b` also writes
+// a.partials[b], its part of in . out over the interior (krylov.hip has
+// the definition of that sum and its order).  The stored outputs are those
+// of launch_halo_stencil, bit for bit.
+hipError_t launch_halo_stencil_dot(const HaloStencilArgs& a, int dt_code,
+                                   unsigned blocks, hipStream_t stream);
+
+// Krylov layer over HaloStencil (krylov.hip; parallel/cg.StencilCG).
+//
+// The elementwise kernels run on the tile grid of the stencil's mode 0: a
+// 256-thread block owns a kStencilTileY x kStencilTileX tile of interior
+// cells of one (ny, nx) plane, `blocks` = nf * levels * tiles_y * tiles_x
+// < 2^24, block index 32-bit, offsets 64-bit.  Only interior cells
+// (w <= y < ny - w, w <= x < nx - w) are read or written.
+//
+// An inner product is the sum over the interior cells of
+// double(a[c]) * double(b[c]), accumulated in float64 in one fixed order
+// (next to krylov_block_sum in krylov_reduce.h); block `b` writes
+// partials[b] and launch_krylov_finish adds the partials into one double.
+struct KrylovArgs {
+  const void* a[kHaloMaxFields];  // dot: a;  update: p;  direction: r
+  const void* b[kHaloMaxFields];  // dot: b;  update: q
+  void* x[kHaloMaxFields];        // update: x
+  void* r[kHaloMaxFields];        // update: r;  direction: p
+  const double* num;              // alpha or beta = *num / *den, 0 when
+  const double* den;              // *den == 0
+  double* partials;               // dot, update
+  long long ny, nx;
+  unsigned levels, tiles_y, tiles_x;
+  int w;
+};
+
+enum KrylovOp : int {
+  KRYLOV_DOT = 0,        // partials of a . b
+  KRYLOV_UPDATE = 1,     // x += alpha p, r -= alpha q, partials of r . r
+  KRYLOV_DIRECTION = 2,  // p = r + beta p
+};
+
+// KRYLOV_DOT takes the four stencil dtypes, the other two DT_F32 and
+// DT_F64 only (anything else launches nothing; the caller checks).
+hipError_t launch_krylov(const KrylovArgs& a, int op, int dt_code,
+                         unsigned blocks, hipStream_t stream);
+
+// One block: result[0] = sum of partials[0, n) in the fixed order;
+// `save`, when not null, first receives the old result[0].
+hipError_t launch_krylov_finish(const double* partials, unsigned n,
+                                double* result, double* save,
+                                hipStream_t stream);

@@ -18,9 +18,20 @@
 // Tiles whose LDS tile lies wholly inside the plane's interior (all but
 // the outermost ring of tiles) take the straight fill and never look at
 // the region table.
+//
+// DOT (apply only, launch_halo_stencil_dot) adds an epilogue after the
+// stores: the block's part of in . out over its output cells, in float64.
+// A thread adds, in the order of its 8 rows and from 0,
+// double(centre of the LDS tile) * double(the output as stored, so after
+// the rounding of a float16 / bfloat16 store); a lane or a row past the
+// interior adds nothing.  Then krylov_block_sum (krylov_reduce.h: shuffle
+// tree, waves in order) and one store to partials[blockIdx.x].  Without
+// DOT the kernel is what it was: every added statement is under
+// `if constexpr (DOT)`.
 
 #include "halo_types.h"
 #include "kernels.h"
+#include "krylov_reduce.h"
 
 #include <cstdint>
 
@@ -39,6 +50,8 @@ static_assert(kStBlock % kStTX == 0 && kStTY % kStWaves == 0,
               "tile shape must divide over the block");
 static_assert(2 * kStencilMaxWidth <= kStTX,
               "the apron columns are filled by one partial pass");
+static_assert(kStBlock == kKrylovBlock,
+              "the dot epilogue reduces over a block of the Krylov size");
 
 template <typename Acc>
 __device__ inline Acc stencil_coef(const HaloStencilArgs& a, int t);
@@ -67,7 +80,7 @@ __device__ inline Acc stencil_halo_cell(const HaloStencilArgs& a,
   return adj_load<T, Acc>(plane + (y * a.nx + x + r.shift));  // OWN: shift 0
 }
 
-template <typename T, typename Acc, int MODE>
+template <typename T, typename Acc, int MODE, bool DOT = false>
 __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
     HaloStencilArgs a) {
   extern __shared__ __align__(16) unsigned char stencil_lds[];
@@ -167,6 +180,23 @@ __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
       if (y < ylim) adj_store<T, Acc>(out + (y * nx + x), acc[i]);
     }
   }
+  if constexpr (DOT) {
+    static_assert(MODE == 0, "the dot epilogue belongs to apply");
+    double sum = 0.0;
+    if (x < xlim) {
+#pragma unroll
+      for (int i = 0; i < kStRows; ++i) {
+        if (oy0 + wrow + i * kStWaves < ylim) {
+          T stored;
+          adj_store<T, Acc>(&stored, acc[i]);
+          sum += (double)tile[base + i * kStWaves * S] *
+                 (double)adj_load<T, Acc>(&stored);
+        }
+      }
+    }
+    sum = krylov_block_sum(sum);
+    if (threadIdx.x == 0) a.partials[blockIdx.x] = sum;
+  }
 }
 
 template <typename T, typename Acc>
@@ -184,7 +214,33 @@ void launch_stencil_t(const HaloStencilArgs& a, int mode, unsigned blocks,
   }
 }
 
+template <typename T, typename Acc>
+void launch_stencil_dot_t(const HaloStencilArgs& a, unsigned blocks,
+                          hipStream_t stream) {
+  const size_t lds = (size_t)(kStTY + 2 * a.w) * (kStTX + 2 * a.w) *
+                     sizeof(Acc);
+  hipLaunchKernelGGL((halo_stencil_kernel<T, Acc, 0, true>), dim3(blocks),
+                     dim3(kStBlock), lds, stream, a);
+}
+
 }  // namespace
+
+hipError_t launch_halo_stencil_dot(const HaloStencilArgs& a, int dt_code,
+                                   unsigned blocks, hipStream_t stream) {
+  if (blocks == 0) return hipSuccess;
+  switch (dt_code) {
+    case DT_F32: launch_stencil_dot_t<float, float>(a, blocks, stream); break;
+    case DT_F64:
+      launch_stencil_dot_t<double, double>(a, blocks, stream);
+      break;
+    case DT_F16:
+      launch_stencil_dot_t<_Float16, float>(a, blocks, stream);
+      break;
+    case DT_BF16: launch_stencil_dot_t<Bf16, float>(a, blocks, stream); break;
+    default: break;  // rejected by the host-side check in bridge.cpp
+  }
+  return hipGetLastError();
+}
 
 hipError_t launch_halo_stencil(const HaloStencilArgs& a, int mode,
                                int dt_code, unsigned blocks,

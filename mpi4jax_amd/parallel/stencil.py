@@ -59,6 +59,7 @@ from torch.autograd.function import once_differentiable
 from .halo import AD_DTYPES, HaloExchanger
 
 MAX_RADIUS = 4
+TILE_Y, TILE_X = 32, 64  # kStencilTileY, kStencilTileX of csrc/kernels.h
 
 
 def _parse_weights(weights):
@@ -114,6 +115,7 @@ class HaloStencil:
         self._tap_dy = [t[0] for t in self._taps]
         self._tap_dx = [t[1] for t in self._taps]
         self._tap_coef = [t[2] for t in self._taps]
+        self._partials = None  # see _partials_buf
 
     @property
     def width(self):
@@ -194,6 +196,113 @@ class HaloStencil:
         else:
             self._adjoint_py(gouts, gins)
         return self._ret(gins)
+
+    # ------------------------------------------------- inner products
+    def _field_list(self, a):
+        fields = (a,) if isinstance(a, torch.Tensor) else tuple(a)
+        self.exchanger._check(fields)
+        return fields
+
+    def _scalar(self):
+        return torch.empty((), dtype=torch.float64,
+                           device=self.exchanger.device)
+
+    def _partials_buf(self):
+        """One float64 slot per block of the native kernels' tile grid
+        (32 x 64 tiles of the interior of every plane), allocated once."""
+        if self._partials is None:
+            ex = self.exchanger
+            w = self._width
+            tiles = (-(-(ex.ny - 2 * w) // TILE_Y)
+                     * -(-(ex.nx - 2 * w) // TILE_X))
+            self._partials = torch.empty(
+                ex.nfields * ex.levels * tiles, dtype=torch.float64,
+                device=ex.device)
+        return self._partials
+
+    def _allreduce_(self, scalar):
+        """Sum a local float64 scalar over the grid's communicator, in
+        place, on the current stream.  One rank with nothing remote: no
+        communicator is touched."""
+        ex = self.exchanger
+        if ex.comm.size > 1 or ex._has_remote:
+            from ..ops.allreduce import allreduce
+            from ..ops.reduce_ops import Op
+
+            scalar.copy_(allreduce(scalar, Op.SUM, comm=ex.comm))
+        return scalar
+
+    def _interior(self, t):
+        ex = self.exchanger
+        w = self._width
+        return t.view(ex.levels, ex.ny, ex.nx)[:, w:ex.ny - w, w:ex.nx - w]
+
+    def _dot_into(self, a, b, result):
+        """``result`` <- the global interior inner product of two checked
+        field lists."""
+        if self._native():
+            from .._backend import rccl
+
+            ex = self.exchanger
+            rccl.ext().halo_interior_dot_nd(
+                list(a), list(b), ex.levels, ex.ny, ex.nx, self._width,
+                self._partials_buf(), result)
+        else:
+            total = None
+            for fa, fb in zip(a, b):
+                s = (self._interior(fa).double()
+                     * self._interior(fb).double()).sum()
+                total = s if total is None else total + s
+            result.copy_(total)
+        return self._allreduce_(result)
+
+    def dot(self, a, b):
+        """The inner product of ``a`` and ``b`` over the interior cells of
+        every level of every field and over every rank of the grid: a 0-d
+        float64 tensor on the fields' device.  ``a`` and ``b`` are each
+        one tensor or a sequence of ``nfields`` tensors; halo cells do not
+        count.  Every term is ``double(a[c]) * double(b[c])`` and all sums
+        are float64, whatever the field dtype.  The native executor adds
+        in one fixed order with no atomics (``csrc/krylov.hip``), so two
+        runs agree bitwise; with more than one rank the local results go
+        through ``allreduce(SUM)`` on the current stream, which makes this
+        a collective."""
+        a, b = self._field_list(a), self._field_list(b)
+        return self._dot_into(a, b, self._scalar())
+
+    def _apply_dot_into(self, fields, outs, result):
+        if self._native():
+            from .._backend import rccl
+
+            ex = self.exchanger
+            comm_id = rccl._handle(ex.comm) if ex._has_remote else -1
+            rccl.ext().halo_stencil_dot_nd(
+                list(fields), list(outs), ex.levels, ex.ny, ex.nx,
+                self._width, self._tap_dy, self._tap_dx, self._tap_coef,
+                ex._send_to, ex._recv_from, ex._local_mask, ex._sbuf,
+                ex._rbuf, comm_id, self._partials_buf(), result)
+            return self._allreduce_(result)
+        self._apply_py(fields, outs)
+        return self._dot_into(fields, outs, result)
+
+    def apply_dot(self, *fields, out=None):
+        """``(out, pAp)``: ``out`` is exactly what :meth:`apply` returns,
+        bit for bit, and ``pAp`` is ``dot(fields, out)``, the product taken
+        with the outputs as stored.  The native executor forms the local
+        sum in the stencil launch itself, followed by one small finish
+        launch."""
+        ex = self.exchanger
+        ex._check(fields)
+        outs = self._outputs(fields, out, zero=True)
+        pap = self._apply_dot_into(fields, outs, self._scalar())
+        return self._ret(outs), pap
+
+    def make_cg(self):
+        """A :class:`~.cg.StencilCG`: conjugate gradients for ``A x = b``
+        with this operator.  float32 and float64 only (``TypeError``)."""
+        from .cg import StencilCG
+
+        return StencilCG(self)
 
     # ------------------------------------------------------------------
     def _call_native(self, entry, ins, outs):

@@ -78,13 +78,13 @@ def build_native(force=False, variant=""):
 
     objs = []
     for src in ["kernels.hip", "shallow_water.hip", "halo.hip",
-                "stencil.hip",
+                "stencil.hip", "krylov.hip",
                 "bridge.cpp"]:
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
         deps = [sp, CSRC / "kernels.h", CSRC / "halo_geom.h",
-                CSRC / "halo_types.h"]
+                CSRC / "halo_types.h", CSRC / "krylov_reduce.h"]
         variant_flags = []
         if variant == "nofma" and src.endswith(".hip"):
             variant_flags = ["-ffp-contract=off"]
