@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <deque>
 #include <mutex>
@@ -1631,6 +1632,81 @@ void halo_stencil_dot_nd(std::vector<at::Tensor> fields,
   watchdog_arm(who, sent.rank, sent.stream);
 }
 
+// One Chebyshev iteration of parallel/chebyshev.StencilChebyshev on the
+// interior: q = A d_in, x += d_in, r -= q, d_out = c1 * d_in + c2 * r, the
+// stencil kernel's CHEB epilogue (HaloChebArgs in kernels.h).  Paths as
+// halo_stencil_dot_nd: one launch with no remote peer, else the
+// exchanger's pack of d_in, the RCCL group and the fused launch reading
+// the receive slots.  No inner product, no scalar on the device: c1 and
+// c2 travel by value.  float32 and float64 only.
+void halo_cheb_step_nd(std::vector<at::Tensor> d_in,
+                       std::vector<at::Tensor> d_out,
+                       std::vector<at::Tensor> x, std::vector<at::Tensor> r,
+                       int64_t levels, int64_t ny, int64_t nx, int64_t width,
+                       std::vector<int64_t> tap_dy,
+                       std::vector<int64_t> tap_dx,
+                       std::vector<double> tap_coef,
+                       std::vector<int64_t> send_to,
+                       std::vector<int64_t> recv_from, int64_t local_mask,
+                       at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id,
+                       double c1, double c2) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_cheb_step_nd");
+  const char* who = "halo_cheb_step_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, d_in, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  const auto st = d_in[0].scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kDouble, who,
+              " supports float32 and float64, got ", st);
+  unsigned blocks = 0;
+  HaloChebArgs a{};
+  static_cast<HaloStencilArgs&>(a) =
+      halo_stencil_args(who, plan, d_in, d_out, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, false, &blocks);
+  const std::vector<at::Tensor>* lists[2] = {&x, &r};
+  for (int li = 0; li < 2; ++li) {
+    TORCH_CHECK((int64_t)lists[li]->size() == plan.nf, who, ": ", plan.nf,
+                " field(s) but ", lists[li]->size(), li ? " of r" : " of x");
+    for (int64_t k = 0; k < plan.nf; ++k) {
+      const auto& f = (*lists[li])[k];
+      TORCH_CHECK(f.is_cuda() && f.is_contiguous() &&
+                      f.sizes() == d_in[k].sizes() &&
+                      f.scalar_type() == st &&
+                      f.device() == d_in[0].device(),
+                  who, ": bad field ", k, li ? " of r" : " of x");
+    }
+  }
+  // d_in, d_out, x and r pairwise disjoint over all fields
+  std::vector<at::Tensor> written(d_out);
+  written.insert(written.end(), x.begin(), x.end());
+  written.insert(written.end(), r.begin(), r.end());
+  krylov_fields_disjoint(who, written, d_in);
+  krylov_no_overlap(who, sbuf, "the send staging buffer", written);
+  krylov_no_overlap(who, rbuf, "the receive staging buffer", written);
+  TORCH_CHECK_VALUE(std::isfinite(c1) && std::isfinite(c2), who,
+                    ": c1 and c2 must be finite, got ", c1, " and ", c2);
+  for (int64_t k = 0; k < plan.nf; ++k) {
+    a.x[k] = x[k].data_ptr();
+    a.r[k] = r[k].data_ptr();
+  }
+  a.c1 = c1;
+  a.c2 = c2;
+  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
+  CommEntry c{};  // looked up only to be checked before the first launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  const int dt = dt_code(d_in[0]);
+  if (!plan.any_remote) {
+    HIP_CHECK(launch_halo_stencil_cheb(a, dt, blocks, cur_stream()));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloChebStepNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_stencil_cheb(a, dt, blocks, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
 // HaloStencil.dot: result = a . b over the interior of this rank.  a and
 // b may be the same tensors.
 void halo_interior_dot_nd(std::vector<at::Tensor> a_fields,
@@ -1818,6 +1894,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_stencil_nd", &halo_stencil_nd);
   m.def("halo_stencil_adjoint_nd", &halo_stencil_adjoint_nd);
   m.def("halo_stencil_dot_nd", &halo_stencil_dot_nd);
+  m.def("halo_cheb_step_nd", &halo_cheb_step_nd);
   m.def("halo_interior_dot_nd", &halo_interior_dot_nd);
   m.def("halo_cg_update_nd", &halo_cg_update_nd);
   m.def("halo_cg_direction_nd", &halo_cg_direction_nd);

@@ -272,6 +272,30 @@ hipError_t launch_halo_stencil(const HaloStencilArgs& a, int mode,
 hipError_t launch_halo_stencil_dot(const HaloStencilArgs& a, int dt_code,
                                    unsigned blocks, hipStream_t stream);
 
+// Mode 0 of the same kernel with its CHEB epilogue: one Chebyshev
+// iteration (parallel/chebyshev.StencilChebyshev) in one launch.  `in` is
+// the current direction d and `out` the next one, a different buffer
+// because other blocks read this block's cells of d as their apron.  With
+// q = A d from the tap loop, per interior cell and in the accumulate type,
+// in this order:
+//   xn = x + d;  rn = r - q;  dn = c1 * d + c2 * rn
+// xn and rn are stored in place, dn to `out`.  Only interior cells of x,
+// r and out are written; c1 and c2 are rounded once to the accumulate
+// type.  float32 and float64 only.
+struct HaloChebArgs : HaloStencilArgs {
+  void* x[kHaloMaxFields];
+  void* r[kHaloMaxFields];
+  double c1, c2;
+};
+
+static_assert(sizeof(HaloChebArgs) < 4096,
+              "the kernel arguments must stay under 4 KiB");
+
+// dt_code must be DT_F32 or DT_F64 (anything else launches nothing; the
+// caller checks).
+hipError_t launch_halo_stencil_cheb(const HaloChebArgs& a, int dt_code,
+                                    unsigned blocks, hipStream_t stream);
+
 // Krylov layer over HaloStencil (krylov.hip; parallel/cg.StencilCG).
 //
 // The elementwise kernels run on the tile grid of the stencil's mode 0: a

@@ -28,12 +28,25 @@
 // tree, waves in order) and one store to partials[blockIdx.x].  Without
 // DOT the kernel is what it was: every added statement is under
 // `if constexpr (DOT)`.
+//
+// CHEB (apply only, float32 / float64, launch_halo_stencil_cheb) turns the
+// launch into one Chebyshev iteration (HaloChebArgs in kernels.h): `in` is
+// the direction d, the tap loop leaves q = A d in registers, and the store
+// becomes x += d, r -= q, out = c1 * d + c2 * r on the thread's interior
+// cells, with d at the centre taken from the LDS tile.  The thread's x
+// and r loads are issued before the tap loop so that their latency hides
+// under it.  Every added statement is under `if constexpr (CHEB)` (the
+// two register arrays are declared outside it, one unused element each
+// otherwise, and the plain store is its else branch), and only then does
+// the kernel take the longer argument struct: the other instantiations
+// compile to the instructions they had.
 
 #include "halo_types.h"
 #include "kernels.h"
 #include "krylov_reduce.h"
 
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
@@ -80,9 +93,10 @@ __device__ inline Acc stencil_halo_cell(const HaloStencilArgs& a,
   return adj_load<T, Acc>(plane + (y * a.nx + x + r.shift));  // OWN: shift 0
 }
 
-template <typename T, typename Acc, int MODE, bool DOT = false>
+template <typename T, typename Acc, int MODE, bool DOT = false,
+          bool CHEB = false>
 __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
-    HaloStencilArgs a) {
+    std::conditional_t<CHEB, HaloChebArgs, HaloStencilArgs> a) {
   extern __shared__ __align__(16) unsigned char stencil_lds[];
   Acc* tile = (Acc*)stencil_lds;
   const int w = a.w;
@@ -159,6 +173,28 @@ __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
   }
   __syncthreads();
 
+  // CHEB: this thread's cells of x and r, loaded ahead of the tap loop
+  [[maybe_unused]] T cheb_x[CHEB ? kStRows : 1];
+  [[maybe_unused]] T cheb_r[CHEB ? kStRows : 1];
+  if constexpr (CHEB) {
+    static_assert(MODE == 0 && !DOT && std::is_same<T, Acc>::value,
+                  "the Chebyshev epilogue belongs to apply in f32 / f64");
+    const long long cx = ox0 + lane;
+    if (cx < nx - w) {
+      const long long pl0 = (long long)l * ny * nx;
+      const T* px = (const T*)a.x[f] + pl0;
+      const T* pr = (const T*)a.r[f] + pl0;
+#pragma unroll
+      for (int i = 0; i < kStRows; ++i) {
+        const long long cy = oy0 + wrow + i * kStWaves;
+        if (cy < ny - w) {
+          cheb_x[i] = px[cy * nx + cx];
+          cheb_r[i] = pr[cy * nx + cx];
+        }
+      }
+    }
+  }
+
   Acc acc[kStRows];
 #pragma unroll
   for (int i = 0; i < kStRows; ++i) acc[i] = Acc(0);
@@ -173,7 +209,25 @@ __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
   const long long ylim = MODE == 0 ? ny - w : ny;
   const long long xlim = MODE == 0 ? nx - w : nx;
   const long long x = ox0 + lane;
-  if (x < xlim) {
+  if constexpr (CHEB) {
+    if (x < xlim) {
+      const Acc c1 = (Acc)a.c1, c2 = (Acc)a.c2;
+      const long long pl0 = (long long)l * ny * nx;
+      T* px = (T*)a.x[f] + pl0;
+      T* pr = (T*)a.r[f] + pl0;
+#pragma unroll
+      for (int i = 0; i < kStRows; ++i) {
+        const long long y = oy0 + wrow + i * kStWaves;
+        if (y < ylim) {
+          const Acc d = tile[base + i * kStWaves * S];
+          const Acc rn = cheb_r[i] - acc[i];
+          px[y * nx + x] = cheb_x[i] + d;
+          pr[y * nx + x] = rn;
+          out[y * nx + x] = c1 * d + c2 * rn;
+        }
+      }
+    }
+  } else if (x < xlim) {
 #pragma unroll
     for (int i = 0; i < kStRows; ++i) {
       const long long y = oy0 + wrow + i * kStWaves;
@@ -223,7 +277,27 @@ void launch_stencil_dot_t(const HaloStencilArgs& a, unsigned blocks,
                      dim3(kStBlock), lds, stream, a);
 }
 
+template <typename T>
+void launch_stencil_cheb_t(const HaloChebArgs& a, unsigned blocks,
+                           hipStream_t stream) {
+  const size_t lds = (size_t)(kStTY + 2 * a.w) * (kStTX + 2 * a.w) *
+                     sizeof(T);
+  hipLaunchKernelGGL((halo_stencil_kernel<T, T, 0, false, true>),
+                     dim3(blocks), dim3(kStBlock), lds, stream, a);
+}
+
 }  // namespace
+
+hipError_t launch_halo_stencil_cheb(const HaloChebArgs& a, int dt_code,
+                                    unsigned blocks, hipStream_t stream) {
+  if (blocks == 0) return hipSuccess;
+  switch (dt_code) {
+    case DT_F32: launch_stencil_cheb_t<float>(a, blocks, stream); break;
+    case DT_F64: launch_stencil_cheb_t<double>(a, blocks, stream); break;
+    default: break;  // rejected by the host-side check in bridge.cpp
+  }
+  return hipGetLastError();
+}
 
 hipError_t launch_halo_stencil_dot(const HaloStencilArgs& a, int dt_code,
                                    unsigned blocks, hipStream_t stream) {

@@ -14,6 +14,8 @@ from .stencil import HaloStencil  # noqa: F401
 from . import stencil  # noqa: F401
 from .cg import CGInfo, StencilCG  # noqa: F401
 from . import cg  # noqa: F401
+from .chebyshev import ChebyshevInfo, StencilChebyshev  # noqa: F401
+from . import chebyshev  # noqa: F401
 from .ddp import average_gradients  # noqa: F401
 from .tp import (  # noqa: F401
     ColumnParallelLinear,

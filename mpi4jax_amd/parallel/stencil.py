@@ -304,6 +304,31 @@ class HaloStencil:
 
         return StencilCG(self)
 
+    def gershgorin_bounds(self):
+        """``(centre - s, centre + s)`` as floats, ``s`` the sum of the
+        magnitudes of the off-centre weights: Gershgorin's interval for
+        the eigenvalues of ``A`` on interior vectors.  It is rigorous for
+        symmetric weights whatever the edges: on a fully periodic grid
+        every row of ``A`` holds exactly these weights, and closed edges
+        with a zero halo leave a principal submatrix of that matrix,
+        whose eigenvalues lie between the same bounds (and decomposed
+        edges do not change the global matrix).  The lower bound is only
+        useful when it is positive, that is for a diagonally dominant
+        stencil such as ``I - nu * lap``."""
+        centre = sum(c for dy, dx, c in self._taps if dy == 0 and dx == 0)
+        s = sum(abs(c) for dy, dx, c in self._taps if dy != 0 or dx != 0)
+        return float(centre - s), float(centre + s)
+
+    def make_chebyshev(self, lmin, lmax):
+        """A :class:`~.chebyshev.StencilChebyshev`: Chebyshev iteration
+        for ``A x = b`` given ``0 < lmin <= lambda(A) <= lmax``
+        (``ValueError`` unless ``0 < lmin < lmax < inf``; nothing checks
+        that the bounds hold).  float32 and float64 only
+        (``TypeError``)."""
+        from .chebyshev import StencilChebyshev
+
+        return StencilChebyshev(self, lmin, lmax)
+
     # ------------------------------------------------------------------
     def _call_native(self, entry, ins, outs):
         from .._backend import rccl
