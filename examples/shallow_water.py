@@ -47,7 +47,9 @@ def main():
 
     m.init()
     comm = m.get_world()
-    device = "cuda" if torch.cuda.is_available() else "cpu"
+    # one process per GPU: with fewer GPUs than ranks (two ranks cannot
+    # share a device through RCCL) the demo runs on the CPU backend
+    device = "cuda" if torch.cuda.device_count() >= comm.size else "cpu"
 
     if args.benchmark:
         nx, ny = args.nx or 3600, args.ny or 1800

@@ -48,7 +48,9 @@ def main():
     m.init()
     comm = m.get_world()
     torch.manual_seed(0)  # same init draws on every rank
-    device = "cuda" if torch.cuda.is_available() else "cpu"
+    # one process per GPU: with fewer GPUs than ranks (two ranks cannot
+    # share a device through RCCL) the demo runs on the CPU backend
+    device = "cuda" if torch.cuda.device_count() >= comm.size else "cpu"
 
     d = args.dim
     dense1 = torch.nn.Linear(d, 2 * d, bias=False).to(device)

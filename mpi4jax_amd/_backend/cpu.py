@@ -50,18 +50,25 @@ def drain_pending(timeout_s=60.0):
     finalize is a bug in the program — after ``timeout_s`` this warns
     loudly and abandons the sends instead of hanging interpreter exit
     (MPI implementations typically abort here)."""
+    import datetime
     import time
     import warnings
 
     deadline = time.monotonic() + timeout_s
     leftover = 0
-    for pl in _PENDING.values():
+    for pl in list(_PENDING.values()):
         for w, _ in pl:
-            while not w.is_completed():
-                if time.monotonic() > deadline:
-                    leftover += 1
-                    break
-                time.sleep(0.005)
+            if w.is_completed():
+                continue
+            # gloo marks a send complete only inside wait(): polling
+            # is_completed() would sit out the whole timeout on a send
+            # that was delivered long ago.  A zero timedelta means "no
+            # timeout" to c10d, hence the 1 ms floor.
+            left = max(deadline - time.monotonic(), 1e-3)
+            try:
+                w.wait(timeout=datetime.timedelta(seconds=left))
+            except RuntimeError:  # gloo: timed out waiting for the send
+                leftover += 1
         pl.clear()
     if leftover:
         warnings.warn(

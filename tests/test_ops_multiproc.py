@@ -383,3 +383,30 @@ def _split_tagged(rank, ws):
 
 def test_split_comm_tagged_isolation_world4():
     run_multiproc(_split_tagged, 4)
+
+
+def _drain_after_delivery(rank, ws):
+    """Sends that a receive has matched must not hold finalize up: gloo
+    reports an isend complete only from wait(), so a drain that polls
+    is_completed() sits out its whole timeout (60 s) in every process
+    that ever sent.  Nothing is in flight after the barrier, so the drain
+    has nothing to wait for; 5 s is slack for a loaded machine."""
+    import time
+
+    from mpi4jax_amd._backend import cpu
+
+    comm = m.get_world()
+    peer = 1 - rank
+    for k in range(3):
+        y = m.sendrecv(torch.full((4,), float(rank + k)), torch.empty(4),
+                       source=peer, dest=peer, comm=comm)
+        assert torch.equal(y, torch.full((4,), float(peer + k)))
+    m.barrier(comm=comm)
+    t0 = time.monotonic()
+    cpu.drain_pending()
+    assert time.monotonic() - t0 < 5.0
+    assert not any(cpu._PENDING.values())
+
+
+def test_drain_does_not_wait_for_delivered_sends():
+    run_multiproc(_drain_after_delivery, 2)

@@ -49,12 +49,11 @@ def test_scan_avg_rejected():
 
 
 def test_sendrecv_device_mismatch():
-    if not torch.cuda.is_available():
-        import pytest as _pytest
-
-        _pytest.skip("needs a GPU to construct the mismatch")
+    # without a GPU a meta tensor is the other device: the check compares
+    # devices before anything touches the template's data
+    other = "cuda" if torch.cuda.is_available() else "meta"
     with pytest.raises(ValueError, match="same device"):
-        m.sendrecv(torch.zeros(3), torch.zeros(3, device="cuda"),
+        m.sendrecv(torch.zeros(3), torch.zeros(3, device=other),
                    source=0, dest=0)
 
 
