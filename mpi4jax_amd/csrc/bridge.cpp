@@ -1834,6 +1834,194 @@ void halo_stencil_adjoint_nd(std::vector<at::Tensor> gouts,
                   std::move(rbuf), comm_id);
 }
 
+// ---- variable-coefficient halo stencil
+// (parallel/varstencil.VariableHaloStencil, varstencil.hip)
+
+// Checks and kernel arguments of the three entries below.  Everything
+// halo_stencil_args asks of the fields, the outputs and the offsets is
+// asked here through it; `coef` is the (ntaps, ny, nx) tensor of
+// coefficients in the accumulate type and `lpb` the levels per block.
+// Raises before anything is enqueued.
+HaloVarStencilArgs halo_varstencil_args(
+    const char* who, const HaloNdPlan& plan,
+    const std::vector<at::Tensor>& fields, const std::vector<at::Tensor>& outs,
+    int64_t levels, int64_t ny, int64_t nx,
+    const std::vector<int64_t>& tap_dy, const std::vector<int64_t>& tap_dx,
+    const at::Tensor& coef, int64_t lpb,
+    const std::vector<int64_t>& recv_from, const at::Tensor& rbuf,
+    bool transposed, unsigned* blocks) {
+  const size_t nt = tap_dy.size();
+  TORCH_CHECK(nt >= 1 && nt <= (size_t)kVarStencilMaxTaps, who,
+              ": the number of taps must be in 1..", kVarStencilMaxTaps);
+  unsigned unused = 0;
+  HaloStencilArgs c =
+      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
+                        tap_dx, std::vector<double>(nt, 0.0), transposed,
+                        &unused);
+  if (!transposed) halo_stencil_regions(c, plan, recv_from, rbuf, nx);
+  const int64_t nf = plan.nf, w = plan.w;
+  const bool f64 = fields[0].scalar_type() == at::kDouble;
+  TORCH_CHECK(coef.is_cuda() && coef.device() == fields[0].device() &&
+                  coef.is_contiguous() && coef.dim() == 3 &&
+                  coef.size(0) == (int64_t)nt && coef.size(1) == ny &&
+                  coef.size(2) == nx &&
+                  coef.scalar_type() == (f64 ? at::kDouble : at::kFloat),
+              who, ": coefficients must be a contiguous (", nt, ", ", ny,
+              ", ", nx, ") ", f64 ? "float64" : "float32",
+              " tensor on the fields' device");
+  krylov_no_overlap(who, coef, "coefficients", outs);
+  TORCH_CHECK_VALUE(lpb >= 1 && lpb <= levels, who,
+                    ": levels per block must be in 1..", levels, ", got ",
+                    lpb);
+  const int64_t ty =
+      4 * (f64 ? kVarStencilRowsF64 : kVarStencilRowsF32);
+  const int64_t org = transposed ? 0 : w;
+  const int64_t tiles_y = (ny - 2 * org + ty - 1) / ty;
+  const int64_t tiles_x = (nx - 2 * org + kStencilTileX - 1) / kStencilTileX;
+  const int64_t chunks = (levels + lpb - 1) / lpb;
+  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
+  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
+                        nf * chunks * (tiles_y * tiles_x) < max_blocks,
+                    who, ": ", nf * chunks, " level chunks of ", tiles_y,
+                    " x ", tiles_x,
+                    " tiles exceed the launch limit of 2^24 blocks");
+  *blocks = (unsigned)(nf * chunks * tiles_y * tiles_x);
+
+  HaloVarStencilArgs a{};
+  for (int64_t k = 0; k < nf; ++k) {
+    a.in[k] = c.in[k];
+    a.out[k] = c.out[k];
+  }
+  for (int k = 0; k < 9; ++k) a.reg[k] = c.reg[k];
+  a.coef = coef.data_ptr();
+  for (size_t t = 0; t < nt; ++t) {
+    a.tap_dy[t] = (int)tap_dy[t];
+    a.tap_dx[t] = (int)tap_dx[t];
+  }
+  a.ny = ny;
+  a.nx = nx;
+  a.levels = (unsigned)levels;
+  a.lpb = (unsigned)lpb;
+  a.chunks = (unsigned)chunks;
+  a.tiles_y = (unsigned)tiles_y;
+  a.tiles_x = (unsigned)tiles_x;
+  a.w = (int)w;
+  a.ntaps = (int)nt;
+  return a;
+}
+
+// Native executor of VariableHaloStencil.apply: halo_stencil_nd with the
+// coefficient tensor in place of tap_coef, and the levels per block.  No
+// remote entry: ONE launch.  Otherwise the exchanger's pack launch, its
+// RCCL group and one launch reading the receive slots.
+void halo_varstencil_nd(std::vector<at::Tensor> fields,
+                        std::vector<at::Tensor> outs, int64_t levels,
+                        int64_t ny, int64_t nx, int64_t width,
+                        std::vector<int64_t> tap_dy,
+                        std::vector<int64_t> tap_dx, at::Tensor coef,
+                        int64_t lpb, std::vector<int64_t> send_to,
+                        std::vector<int64_t> recv_from, int64_t local_mask,
+                        at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_nd");
+  const char* who = "halo_varstencil_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  const HaloVarStencilArgs a = halo_varstencil_args(
+      who, plan, fields, outs, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
+      recv_from, rbuf, false, &blocks);
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    HIP_CHECK(launch_halo_varstencil(a, 0, dt, blocks, cur_stream()));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloVarStencilNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_varstencil(a, 0, dt, blocks, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// VariableHaloStencil.apply_dot: halo_varstencil_nd with the kernel's DOT
+// epilogue, then the finish launch over the new kernel's block count.
+void halo_varstencil_dot_nd(std::vector<at::Tensor> fields,
+                            std::vector<at::Tensor> outs, int64_t levels,
+                            int64_t ny, int64_t nx, int64_t width,
+                            std::vector<int64_t> tap_dy,
+                            std::vector<int64_t> tap_dx, at::Tensor coef,
+                            int64_t lpb, std::vector<int64_t> send_to,
+                            std::vector<int64_t> recv_from,
+                            int64_t local_mask, at::Tensor sbuf,
+                            at::Tensor rbuf, int64_t comm_id,
+                            at::Tensor partials, at::Tensor result) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_dot_nd");
+  const char* who = "halo_varstencil_dot_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  HaloVarStencilArgs a = halo_varstencil_args(
+      who, plan, fields, outs, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
+      recv_from, rbuf, false, &blocks);
+  const at::Device dev = fields[0].device();
+  a.partials = krylov_partials(who, partials, dev, blocks);
+  double* res = krylov_scalar(who, "result", result, dev);
+  krylov_no_overlap(who, partials, "partials", outs);
+  krylov_no_overlap(who, result, "result", outs);
+  krylov_no_overlap(who, result, "result", {partials});
+  CommEntry c{};  // looked up only to be checked before the first launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    hipStream_t stream = cur_stream();
+    HIP_CHECK(launch_halo_varstencil(a, 2, dt, blocks, stream));
+    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloVarStencilDotNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_varstencil(a, 2, dt, blocks, sent.stream));
+  HIP_CHECK(
+      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// Native executor of VariableHaloStencil.adjoint: one launch of the
+// kernel's transposed mode writes every cell of `gins`; halo_adjoint_nd
+// then runs in place on them.
+void halo_varstencil_adjoint_nd(std::vector<at::Tensor> gouts,
+                                std::vector<at::Tensor> gins, int64_t levels,
+                                int64_t ny, int64_t nx, int64_t width,
+                                std::vector<int64_t> tap_dy,
+                                std::vector<int64_t> tap_dx, at::Tensor coef,
+                                int64_t lpb, std::vector<int64_t> send_to,
+                                std::vector<int64_t> recv_from,
+                                int64_t local_mask, at::Tensor sbuf,
+                                at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_adjoint_nd");
+  const char* who = "halo_varstencil_adjoint_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  const HaloVarStencilArgs a = halo_varstencil_args(
+      who, plan, gouts, gins, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
+      recv_from, rbuf, true, &blocks);
+  // everything halo_adjoint_nd will ask of `gins`, before the launch
+  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
+  CommEntry c{};  // looked up only to be checked before the launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  HIP_CHECK(launch_halo_varstencil(a, 1, dt_code(gouts[0]), blocks,
+                                   cur_stream()));
+  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
+                  std::move(recv_from), local_mask, std::move(sbuf),
+                  std::move(rbuf), comm_id);
+}
+
 // direct access to the combine kernel (used by gpu numerics tests)
 void combine(at::Tensor dst, at::Tensor a, at::Tensor b, int64_t op) {
   check_pair(dst, a);
@@ -1895,6 +2083,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_stencil_adjoint_nd", &halo_stencil_adjoint_nd);
   m.def("halo_stencil_dot_nd", &halo_stencil_dot_nd);
   m.def("halo_cheb_step_nd", &halo_cheb_step_nd);
+  m.def("halo_varstencil_nd", &halo_varstencil_nd);
+  m.def("halo_varstencil_dot_nd", &halo_varstencil_dot_nd);
+  m.def("halo_varstencil_adjoint_nd", &halo_varstencil_adjoint_nd);
   m.def("halo_interior_dot_nd", &halo_interior_dot_nd);
   m.def("halo_cg_update_nd", &halo_cg_update_nd);
   m.def("halo_cg_direction_nd", &halo_cg_direction_nd);

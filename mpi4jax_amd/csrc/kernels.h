@@ -296,6 +296,54 @@ static_assert(sizeof(HaloChebArgs) < 4096,
 hipError_t launch_halo_stencil_cheb(const HaloChebArgs& a, int dt_code,
                                     unsigned blocks, hipStream_t stream);
 
+// Variable-coefficient halo stencil of
+// parallel/varstencil.VariableHaloStencil (varstencil.hip).  The taps are
+// ntaps <= kVarStencilMaxTaps offsets (dy, dx), |dy|, |dx| <= w, and `coef`
+// holds one (ny, nx) plane of the accumulate type per tap, shared by every
+// level of every field; only its interior cells are read.
+//
+// A workgroup owns one (4 * rows) x kStencilTileX tile of output cells for
+// levels [chunk * lpb, min(levels, (chunk + 1) * lpb)) of one field, with
+// rows = kVarStencilRowsF32 for float accumulation and kVarStencilRowsF64
+// for double; tiles_y counts tiles of that height.  A thread keeps the
+// coefficients of its outputs in registers for the whole march.  The block
+// index decodes, fastest first, to (tile x, tile y, chunk, field):
+// `blocks` = nf * chunks * tiles_y * tiles_x < 2^24, 32-bit; offsets into
+// a field, a slot or `coef` are 64-bit.
+//
+// mode 0 (apply): out[l, j, i] = sum_t K_t[j, i] * v[l, j + dy_t, i + dx_t]
+// on interior cells, halo cells of v read through the region table as in
+// HaloStencilArgs; the sum is formed from 0 in tap order.
+// mode 1 (transposed): every cell p is written with the sum, in the same
+// order, of K_t[p - o_t] * in[p - o_t] over the taps whose source cell
+// p - o_t is interior; the region table is not used.
+// mode 2: mode 0, and block `b` also writes partials[b], its part of
+// in . out over its interior cells in float64: a thread adds
+// double(in) * double(out as stored) level by level and row by row, then
+// krylov_block_sum.  The stored outputs are those of mode 0, bit for bit.
+constexpr int kVarStencilMaxTaps = 13;
+constexpr int kVarStencilRowsF32 = 8;
+constexpr int kVarStencilRowsF64 = 4;
+
+struct HaloVarStencilArgs {
+  const void* in[kHaloMaxFields];
+  void* out[kHaloMaxFields];
+  StencilRegion reg[9];
+  const void* coef;  // (ntaps, ny, nx) in the accumulate type
+  int tap_dy[kVarStencilMaxTaps];
+  int tap_dx[kVarStencilMaxTaps];
+  long long ny, nx;
+  unsigned levels, lpb, chunks, tiles_y, tiles_x;
+  int w, ntaps;
+  double* partials;  // mode 2: one slot per block
+};
+
+// dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16.  Returns the launch's
+// status.
+hipError_t launch_halo_varstencil(const HaloVarStencilArgs& a, int mode,
+                                  int dt_code, unsigned blocks,
+                                  hipStream_t stream);
+
 // Krylov layer over HaloStencil (krylov.hip; parallel/cg.StencilCG).
 //
 // The elementwise kernels run on the tile grid of the stencil's mode 0: a

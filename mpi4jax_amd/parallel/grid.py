@@ -193,6 +193,25 @@ class CartesianGrid:
         return HaloStencil(self, shape, dtype, device, weights,
                            nfields=nfields, _force_remote=_force_remote)
 
+    def make_variable_stencil(self, shape, dtype, device, offsets,
+                              coefficients, nfields=1, _force_remote=False,
+                              _levels_per_block=None):
+        """Build a :class:`~.varstencil.VariableHaloStencil`: ``offsets``
+        is a list of ``1 <= T <= 13`` distinct ``(dy, dx)`` pairs of radius
+        ``1..4`` and ``coefficients`` a real ``(T, ny, nx)`` tensor, one
+        plane per tap, local to the rank and shared by every level and
+        field.  ``out[l, j, i] = sum_t K_t[j, i] * v[l, j + dy_t, i + dx_t]``
+        through a halo exchange of the radius' width, with a native
+        adjoint, ``apply_dot`` and ``make_cg``.  ``shape``, ``nfields`` and
+        ``_force_remote`` are those of :meth:`make_halo_exchanger`.
+        """
+        from .varstencil import VariableHaloStencil
+
+        return VariableHaloStencil(
+            self, shape, dtype, device, offsets, coefficients,
+            nfields=nfields, _force_remote=_force_remote,
+            _levels_per_block=_levels_per_block)
+
     def _halo_exchange_impl(self, out):
         # imported here to avoid a circular import at package init
         from ..ops.sendrecv import sendrecv

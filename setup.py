@@ -78,7 +78,7 @@ def build_native(force=False, variant=""):
 
     objs = []
     for src in ["kernels.hip", "shallow_water.hip", "halo.hip",
-                "stencil.hip", "krylov.hip",
+                "stencil.hip", "krylov.hip", "varstencil.hip",
                 "bridge.cpp"]:
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
@@ -88,6 +88,10 @@ def build_native(force=False, variant=""):
         variant_flags = []
         if variant == "nofma" and src.endswith(".hip"):
             variant_flags = ["-ffp-contract=off"]
+        if src == "varstencil.hip":
+            # no packed float32 arithmetic in this kernel's tap loop
+            variant_flags += ["-Xclang", "-target-feature", "-Xclang",
+                              "-packed-fp32-ops"]
         if force or _newer(op, deps):
             extra = ["-x", "hip"] if src.endswith(".cpp") else []
             # bridge.cpp is host-only but compiled as hip for runtime hdrs
