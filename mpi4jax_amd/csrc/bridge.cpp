@@ -2022,6 +2022,208 @@ void halo_varstencil_adjoint_nd(std::vector<at::Tensor> gouts,
                   std::move(rbuf), comm_id);
 }
 
+// ---- 3-D halo stencil (parallel/stencil3d.HaloStencil3D, stencil3d.hip)
+
+// Checks and kernel arguments of the three entries below.  Everything
+// halo_stencil_args asks of the fields, the outputs and the in-plane
+// offsets is asked here through it.  `nz` is the z extent (levels =
+// columns * nz), `tap_dz` the taps' z offsets, sorted, `zc` the output
+// planes per block.  Raises before anything is enqueued.
+HaloStencil3dArgs halo_stencil3d_args(
+    const char* who, const HaloNdPlan& plan,
+    const std::vector<at::Tensor>& fields, const std::vector<at::Tensor>& outs,
+    int64_t levels, int64_t nz, int64_t ny, int64_t nx,
+    const std::vector<int64_t>& tap_dz, const std::vector<int64_t>& tap_dy,
+    const std::vector<int64_t>& tap_dx, const std::vector<double>& tap_coef,
+    int64_t zc, bool periodic_z, const std::vector<int64_t>& recv_from,
+    const at::Tensor& rbuf, bool transposed, unsigned* blocks) {
+  const size_t nt = tap_dz.size();
+  TORCH_CHECK(nt >= 1 && nt <= (size_t)kStencil3dMaxTaps &&
+                  tap_dy.size() == nt,
+              who, ": the four tap lists must have one length in 1..",
+              kStencil3dMaxTaps);
+  unsigned unused = 0;
+  HaloStencilArgs c =
+      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
+                        tap_dx, tap_coef, transposed, &unused);
+  if (!transposed) halo_stencil_regions(c, plan, recv_from, rbuf, nx);
+  int64_t rz = 0;
+  for (size_t t = 0; t < nt; ++t) {
+    rz = std::max(rz, std::max(tap_dz[t], -tap_dz[t]));
+    TORCH_CHECK(t == 0 || tap_dz[t - 1] <= tap_dz[t], who,
+                ": the taps must be sorted by dz");
+  }
+  TORCH_CHECK(rz <= kStencil3dMaxRz, who, ": z radius ", rz, " exceeds ",
+              kStencil3dMaxRz);
+  TORCH_CHECK_VALUE(nz >= 1 && levels % nz == 0, who, ": ", levels,
+                    " levels are not whole columns of nz = ", nz);
+  TORCH_CHECK_VALUE(!periodic_z || nz >= 2 * rz + 1, who,
+                    ": periodic z needs nz >= ", 2 * rz + 1, ", got ", nz);
+  TORCH_CHECK_VALUE(zc >= 1 && zc <= nz, who,
+                    ": planes per block must be in 1..", nz, ", got ", zc);
+  const int64_t nf = plan.nf, w = plan.w;
+  const int64_t columns = levels / nz;
+  const int64_t chunks = (nz + zc - 1) / zc;
+  const int64_t tiles = (int64_t)c.tiles_y * c.tiles_x;
+  // chunks <= nz, so this grid has at most the nf * levels * tiles blocks
+  // that halo_stencil_args has checked against the launch limit of 2^24
+  *blocks = (unsigned)(nf * columns * chunks * tiles);
+
+  HaloStencil3dArgs a{};
+  for (int64_t k = 0; k < nf; ++k) {
+    a.in[k] = c.in[k];
+    a.out[k] = c.out[k];
+  }
+  for (int k = 0; k < 9; ++k) a.reg[k] = c.reg[k];
+  const bool f64 = fields[0].scalar_type() == at::kDouble;
+  for (size_t t = 0; t < nt; ++t) {
+    if (f64) {
+      a.coef.f64[t] = c.coef.f64[t];
+    } else {
+      a.coef.f32[t] = c.coef.f32[t];
+    }
+    a.tap_off[t] = c.tap_off[t];
+  }
+  // tap_begin[j]: the first tap with dz >= j - rz
+  for (int64_t j = 0; j <= 2 * rz + 1; ++j) {
+    size_t t = 0;
+    while (t < nt && tap_dz[t] < j - rz) ++t;
+    a.tap_begin[j] = (int)t;
+  }
+  a.ny = ny;
+  a.nx = nx;
+  a.levels = (unsigned)levels;
+  a.nz = (unsigned)nz;
+  a.columns = (unsigned)columns;
+  a.zc = (unsigned)zc;
+  a.chunks = (unsigned)chunks;
+  a.tiles_y = c.tiles_y;
+  a.tiles_x = c.tiles_x;
+  a.w = (int)w;
+  a.rz = (int)rz;
+  a.ntaps = (int)nt;
+  a.periodic_z = periodic_z ? 1 : 0;
+  return a;
+}
+
+// Native executor of HaloStencil3D.apply: halo_stencil_nd's launch
+// sequence with the 3-D kernel.  No remote entry: ONE launch.  Otherwise
+// the exchanger's pack launch, its RCCL group and one launch reading the
+// receive slots.
+void halo_stencil3d_nd(std::vector<at::Tensor> fields,
+                       std::vector<at::Tensor> outs, int64_t levels,
+                       int64_t nz, int64_t ny, int64_t nx, int64_t width,
+                       std::vector<int64_t> tap_dz,
+                       std::vector<int64_t> tap_dy,
+                       std::vector<int64_t> tap_dx,
+                       std::vector<double> tap_coef, int64_t zc,
+                       bool periodic_z, std::vector<int64_t> send_to,
+                       std::vector<int64_t> recv_from, int64_t local_mask,
+                       at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_nd");
+  const char* who = "halo_stencil3d_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  const HaloStencil3dArgs a = halo_stencil3d_args(
+      who, plan, fields, outs, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
+      tap_coef, zc, periodic_z, recv_from, rbuf, false, &blocks);
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    HIP_CHECK(launch_halo_stencil3d(a, 0, dt, blocks, cur_stream()));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloStencil3dNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_stencil3d(a, 0, dt, blocks, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// HaloStencil3D.apply_dot: halo_stencil3d_nd with the kernel's DOT
+// epilogue, then the finish launch over this kernel's block count.
+void halo_stencil3d_dot_nd(std::vector<at::Tensor> fields,
+                           std::vector<at::Tensor> outs, int64_t levels,
+                           int64_t nz, int64_t ny, int64_t nx, int64_t width,
+                           std::vector<int64_t> tap_dz,
+                           std::vector<int64_t> tap_dy,
+                           std::vector<int64_t> tap_dx,
+                           std::vector<double> tap_coef, int64_t zc,
+                           bool periodic_z, std::vector<int64_t> send_to,
+                           std::vector<int64_t> recv_from,
+                           int64_t local_mask, at::Tensor sbuf,
+                           at::Tensor rbuf, int64_t comm_id,
+                           at::Tensor partials, at::Tensor result) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_dot_nd");
+  const char* who = "halo_stencil3d_dot_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  HaloStencil3dArgs a = halo_stencil3d_args(
+      who, plan, fields, outs, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
+      tap_coef, zc, periodic_z, recv_from, rbuf, false, &blocks);
+  const at::Device dev = fields[0].device();
+  a.partials = krylov_partials(who, partials, dev, blocks);
+  double* res = krylov_scalar(who, "result", result, dev);
+  krylov_no_overlap(who, partials, "partials", outs);
+  krylov_no_overlap(who, result, "result", outs);
+  krylov_no_overlap(who, result, "result", {partials});
+  CommEntry c{};  // looked up only to be checked before the first launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  const int dt = dt_code(fields[0]);
+  if (!plan.any_remote) {
+    hipStream_t stream = cur_stream();
+    HIP_CHECK(launch_halo_stencil3d(a, 2, dt, blocks, stream));
+    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
+    return;
+  }
+  const HaloNdSent sent =
+      halo_exchange_send("HaloStencil3dDotNd", plan, levels, ny, nx, send_to,
+                         recv_from, local_mask, sbuf, rbuf, comm_id);
+  HIP_CHECK(launch_halo_stencil3d(a, 2, dt, blocks, sent.stream));
+  HIP_CHECK(
+      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// Native executor of HaloStencil3D.adjoint: one launch of the kernel's
+// transposed mode writes every cell of `gins`; halo_adjoint_nd then runs
+// in place on them.
+void halo_stencil3d_adjoint_nd(std::vector<at::Tensor> gouts,
+                               std::vector<at::Tensor> gins, int64_t levels,
+                               int64_t nz, int64_t ny, int64_t nx,
+                               int64_t width, std::vector<int64_t> tap_dz,
+                               std::vector<int64_t> tap_dy,
+                               std::vector<int64_t> tap_dx,
+                               std::vector<double> tap_coef, int64_t zc,
+                               bool periodic_z, std::vector<int64_t> send_to,
+                               std::vector<int64_t> recv_from,
+                               int64_t local_mask, at::Tensor sbuf,
+                               at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_adjoint_nd");
+  const char* who = "halo_stencil3d_adjoint_nd";
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
+                                       send_to, recv_from, local_mask, sbuf,
+                                       rbuf);
+  unsigned blocks = 0;
+  const HaloStencil3dArgs a = halo_stencil3d_args(
+      who, plan, gouts, gins, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
+      tap_coef, zc, periodic_z, recv_from, rbuf, true, &blocks);
+  // everything halo_adjoint_nd will ask of `gins`, before the launch
+  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
+  CommEntry c{};  // looked up only to be checked before the launch
+  halo_peers(plan, comm_id, send_to, recv_from, &c);
+
+  HIP_CHECK(launch_halo_stencil3d(a, 1, dt_code(gouts[0]), blocks,
+                                  cur_stream()));
+  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
+                  std::move(recv_from), local_mask, std::move(sbuf),
+                  std::move(rbuf), comm_id);
+}
+
 // direct access to the combine kernel (used by gpu numerics tests)
 void combine(at::Tensor dst, at::Tensor a, at::Tensor b, int64_t op) {
   check_pair(dst, a);
@@ -2086,6 +2288,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_varstencil_nd", &halo_varstencil_nd);
   m.def("halo_varstencil_dot_nd", &halo_varstencil_dot_nd);
   m.def("halo_varstencil_adjoint_nd", &halo_varstencil_adjoint_nd);
+  m.def("halo_stencil3d_nd", &halo_stencil3d_nd);
+  m.def("halo_stencil3d_dot_nd", &halo_stencil3d_dot_nd);
+  m.def("halo_stencil3d_adjoint_nd", &halo_stencil3d_adjoint_nd);
   m.def("halo_interior_dot_nd", &halo_interior_dot_nd);
   m.def("halo_cg_update_nd", &halo_cg_update_nd);
   m.def("halo_cg_direction_nd", &halo_cg_direction_nd);

@@ -344,6 +344,62 @@ hipError_t launch_halo_varstencil(const HaloVarStencilArgs& a, int mode,
                                   int dt_code, unsigned blocks,
                                   hipStream_t stream);
 
+// 3-D halo stencil of parallel/stencil3d.HaloStencil3D (stencil3d.hip).
+// A field is `columns` independent (nz, ny, nx) columns, levels = columns *
+// nz planes in the exchanger's layout; z is local and has no halo.  The
+// taps are ntaps <= kStencil3dMaxTaps triples (dz, dy, dx), |dz| <= rz <= 2,
+// |dy|, |dx| <= w, sorted by dz (tap_begin[j] is the first tap of
+// dz = j - rz, tap_begin[2 rz + 1] = ntaps) and in the order they are added
+// inside one dz; `tap_off` is dy * (kStencilTileX + 2 * w) + dx, negated
+// for mode 1.
+//
+// A workgroup owns one kStencilTileY x kStencilTileX tile of one column for
+// the output planes [chunk * zc, min(nz, (chunk + 1) * zc)) and marches
+// along z with one input plane resident in LDS (double-buffered) and
+// 2 rz + 1 output planes in registers.  The block index decodes, fastest
+// first, to (tile x, tile y, chunk, column, field): `blocks` = nf * columns
+// * chunks * tiles_y * tiles_x < 2^24, 32-bit; offsets into a field or a
+// slot are 64-bit.
+//
+// A source plane outside [0, nz) is taken modulo nz when periodic_z is set
+// (the caller checks nz >= 2 rz + 1); otherwise its taps are not formed.
+//
+// mode 0 (apply): out[b, k, j, i] = sum_t K_t * v[b, k + dz_t, j + dy_t,
+// i + dx_t] on interior (j, i), halo cells of v read through the region
+// table as in HaloStencilArgs; the sum is formed from 0 in tap order.
+// mode 1 (transposed): every cell p of every plane k is written with the
+// sum, in the same order, of K_t * in[b, k - dz_t, p - (dy_t, dx_t)] over
+// the taps whose source cell is interior; the region table is not used.
+// mode 2: mode 0, and block `b` also writes partials[b], its part of
+// in . out over its interior cells in float64: a thread adds
+// double(in) * double(out as stored) plane by plane from z0 upward and row
+// by row, then krylov_block_sum.  The stored outputs are those of mode 0,
+// bit for bit.
+constexpr int kStencil3dMaxTaps = 32;
+constexpr int kStencil3dMaxRz = 2;
+
+struct HaloStencil3dArgs {
+  const void* in[kHaloMaxFields];
+  void* out[kHaloMaxFields];
+  StencilRegion reg[9];
+  union {  // coefficients in the accumulate type
+    double f64[kStencil3dMaxTaps];
+    float f32[kStencil3dMaxTaps];
+  } coef;
+  int tap_off[kStencil3dMaxTaps];
+  int tap_begin[2 * kStencil3dMaxRz + 2];
+  long long ny, nx;
+  unsigned levels, nz, columns, zc, chunks, tiles_y, tiles_x;
+  int w, rz, ntaps, periodic_z;
+  double* partials;  // mode 2: one slot per block
+};
+
+// dt_code must be DT_F32, DT_F64, DT_F16 or DT_BF16, a.rz in 0..2.  Returns
+// the launch's status.
+hipError_t launch_halo_stencil3d(const HaloStencil3dArgs& a, int mode,
+                                 int dt_code, unsigned blocks,
+                                 hipStream_t stream);
+
 // Krylov layer over HaloStencil (krylov.hip; parallel/cg.StencilCG).
 //
 // The elementwise kernels run on the tile grid of the stencil's mode 0: a

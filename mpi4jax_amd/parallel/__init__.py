@@ -14,6 +14,8 @@ from .stencil import HaloStencil  # noqa: F401
 from . import stencil  # noqa: F401
 from .varstencil import VariableHaloStencil  # noqa: F401
 from . import varstencil  # noqa: F401
+from .stencil3d import HaloStencil3D  # noqa: F401
+from . import stencil3d  # noqa: F401
 from .cg import CGInfo, StencilCG  # noqa: F401
 from . import cg  # noqa: F401
 from .chebyshev import ChebyshevInfo, StencilChebyshev  # noqa: F401

@@ -212,6 +212,26 @@ class CartesianGrid:
             nfields=nfields, _force_remote=_force_remote,
             _levels_per_block=_levels_per_block)
 
+    def make_stencil3d(self, shape, dtype, device, weights, nfields=1,
+                       z_boundary="zero", _force_remote=False,
+                       _z_chunk=None):
+        """Build a :class:`~.stencil3d.HaloStencil3D`: ``shape`` is
+        ``(..., nz, ny, nx)``, decomposed in ``(y, x)`` and local in z, and
+        ``weights`` a real ``(2rz+1, 2r+1, 2r+1)`` table, ``0 <= rz <= 2``
+        and ``1 <= r <= 4``, with at most 32 non-zero entries; entry
+        ``[a][b][c]`` multiplies the cell at offset ``(a-rz, b-r, c-r)`` in
+        ``(z, y, x)``.  ``z_boundary`` is ``"zero"`` (planes outside
+        ``[0, nz)`` add nothing) or ``"periodic"`` (``nz >= 2rz+1``).  It
+        has a native adjoint, ``apply_dot`` and ``make_cg``.  ``nfields``
+        and ``_force_remote`` are those of :meth:`make_halo_exchanger`.
+        """
+        from .stencil3d import HaloStencil3D
+
+        return HaloStencil3D(
+            self, shape, dtype, device, weights, nfields=nfields,
+            z_boundary=z_boundary, _force_remote=_force_remote,
+            _z_chunk=_z_chunk)
+
     def _halo_exchange_impl(self, out):
         # imported here to avoid a circular import at package init
         from ..ops.sendrecv import sendrecv
