@@ -1800,6 +1800,126 @@ void halo_cg_direction_nd(std::vector<at::Tensor> p,
                           cur_stream()));
 }
 
+// ---- vertical line solves (parallel/zline.ZLineSolver, zline.hip)
+
+// Field, geometry and table checks of the two entries below; `lists` as in
+// krylov_args.  No exchange: both run on the current stream.
+ZLineArgs zline_args(const char* who,
+                     const std::vector<const std::vector<at::Tensor>*>& lists,
+                     int64_t levels, int64_t nz, int64_t ny, int64_t nx,
+                     int64_t w, const at::Tensor& tables, bool periodic,
+                     int64_t lds_planes, unsigned* blocks) {
+  unsigned unused = 0;
+  krylov_args(who, lists, levels, ny, nx, w, true, &unused);
+  const at::Tensor& f0 = (*lists[0])[0];
+  TORCH_CHECK(nz >= 1 && levels % nz == 0, who, ": nz = ", nz,
+              " does not divide ", levels, " levels");
+  TORCH_CHECK(tables.is_cuda() && tables.device() == f0.device() &&
+                  tables.scalar_type() == f0.scalar_type() &&
+                  tables.is_contiguous() && tables.dim() == 2 &&
+                  tables.size(0) == 4 && tables.size(1) == nz,
+              who, ": tables must be a contiguous (4, ", nz,
+              ") tensor of the fields' dtype on their device");
+  const int64_t per_plane = (int64_t)kZlineBlock * f0.element_size();
+  TORCH_CHECK_VALUE(0 <= lds_planes && lds_planes <= nz &&
+                        lds_planes * per_plane <= kZlineMaxLds,
+                    who, ": lds_planes must be in 0..min(nz, ",
+                    kZlineMaxLds / per_plane, "), got ", lds_planes);
+  const int64_t nf = (int64_t)lists[0]->size();
+  const int64_t columns = levels / nz;
+  const int64_t tiles_y = (ny - 2 * w + kZlineTileY - 1) / kZlineTileY;
+  const int64_t tiles_x = (nx - 2 * w + kZlineTileX - 1) / kZlineTileX;
+  const int64_t max_blocks = ((int64_t)1 << 32) / kZlineBlock;
+  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
+                        nf * columns * (tiles_y * tiles_x) < max_blocks,
+                    who, ": ", nf * columns, " columns of ", tiles_y, " x ",
+                    tiles_x, " tiles exceed the launch limit of 2^24 blocks");
+  *blocks = (unsigned)(nf * columns * tiles_y * tiles_x);
+  ZLineArgs a{};
+  a.tables = tables.data_ptr();
+  a.ny = ny;
+  a.nx = nx;
+  a.nz = (unsigned)nz;
+  a.columns = (unsigned)columns;
+  a.tiles_y = (unsigned)tiles_y;
+  a.tiles_x = (unsigned)tiles_x;
+  a.lds_planes = (unsigned)lds_planes;
+  a.w = (int)w;
+  a.periodic = periodic ? 1 : 0;
+  return a;
+}
+
+// ZLineSolver.solve: z = T^{-1} r on the interior columns; the halo of z
+// is not written.
+void halo_zline_solve_nd(std::vector<at::Tensor> r, std::vector<at::Tensor> z,
+                         int64_t levels, int64_t nz, int64_t ny, int64_t nx,
+                         int64_t width, at::Tensor tables, bool periodic,
+                         int64_t lds_planes) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_zline_solve_nd");
+  const char* who = "halo_zline_solve_nd";
+  unsigned blocks = 0;
+  ZLineArgs a = zline_args(who, {&r, &z}, levels, nz, ny, nx, width, tables,
+                           periodic, lds_planes, &blocks);
+  krylov_fields_disjoint(who, z, r);
+  krylov_no_overlap(who, tables, "tables", z);
+  for (size_t k = 0; k < r.size(); ++k) {
+    a.r[k] = r[k].data_ptr();
+    a.z[k] = z[k].data_ptr();
+  }
+  HIP_CHECK(launch_zline(a, ZLINE_SOLVE, dt_code(r[0]), blocks,
+                         cur_stream()));
+}
+
+// The update step of line-preconditioned CG in one launch plus two finish
+// launches: alpha = rz / pq (0 when pq == 0), x += alpha p, r -= alpha q,
+// z = T^{-1} r; then rr = this rank's r . r, rz_old = rz and rz = this
+// rank's r . z, both on the stored r and z.  `partials` has two slots per
+// block.
+void halo_zline_pcg_update_nd(
+    std::vector<at::Tensor> x, std::vector<at::Tensor> r,
+    std::vector<at::Tensor> p, std::vector<at::Tensor> q,
+    std::vector<at::Tensor> z, int64_t levels, int64_t nz, int64_t ny,
+    int64_t nx, int64_t width, at::Tensor tables, bool periodic,
+    int64_t lds_planes, at::Tensor rz, at::Tensor pq, at::Tensor rz_old,
+    at::Tensor rr, at::Tensor partials) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_zline_pcg_update_nd");
+  const char* who = "halo_zline_pcg_update_nd";
+  unsigned blocks = 0;
+  ZLineArgs a = zline_args(who, {&x, &r, &p, &q, &z}, levels, nz, ny, nx,
+                           width, tables, periodic, lds_planes, &blocks);
+  const at::Device dev = x[0].device();
+  a.partials = krylov_partials(who, partials, dev, 2 * blocks);
+  a.num = krylov_scalar(who, "rz", rz, dev);
+  a.den = krylov_scalar(who, "pq", pq, dev);
+  double* old = krylov_scalar(who, "rz_old", rz_old, dev);
+  double* res_rr = krylov_scalar(who, "rr", rr, dev);
+  std::vector<at::Tensor> written(x), read(p);
+  written.insert(written.end(), r.begin(), r.end());
+  written.insert(written.end(), z.begin(), z.end());
+  read.insert(read.end(), q.begin(), q.end());
+  krylov_fields_disjoint(who, written, read);
+  const at::Tensor* small[6] = {&rz, &pq, &rz_old, &rr, &partials, &tables};
+  const char* names[6] = {"rz", "pq", "rz_old", "rr", "partials", "tables"};
+  for (int i = 0; i < 6; ++i) {
+    krylov_no_overlap(who, *small[i], names[i], written);
+    for (int j = 0; j < i; ++j) {
+      krylov_no_overlap(who, *small[i], names[i], {*small[j]});
+    }
+  }
+  for (size_t k = 0; k < x.size(); ++k) {
+    a.p[k] = p[k].data_ptr();
+    a.q[k] = q[k].data_ptr();
+    a.x[k] = x[k].data_ptr();
+    a.r[k] = r[k].data_ptr();
+    a.z[k] = z[k].data_ptr();
+  }
+  hipStream_t stream = cur_stream();
+  HIP_CHECK(launch_zline(a, ZLINE_PCG_UPDATE, dt_code(x[0]), blocks, stream));
+  HIP_CHECK(launch_krylov_finish(a.partials, blocks, res_rr, nullptr, stream));
+  HIP_CHECK(launch_krylov_finish(a.partials + blocks, blocks,
+                                 (double*)a.num, old, stream));
+}
+
 // Native executor of HaloStencil.adjoint: gins = E^T . S^T . P_int (gouts).
 // One launch of the stencil kernel's transposed mode writes every cell of
 // `gins`; halo_adjoint_nd then runs in place on them.
@@ -2294,4 +2414,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_interior_dot_nd", &halo_interior_dot_nd);
   m.def("halo_cg_update_nd", &halo_cg_update_nd);
   m.def("halo_cg_direction_nd", &halo_cg_direction_nd);
+  m.def("halo_zline_solve_nd", &halo_zline_solve_nd);
+  m.def("halo_zline_pcg_update_nd", &halo_zline_pcg_update_nd);
 }

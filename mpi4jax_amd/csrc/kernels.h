@@ -441,3 +441,75 @@ hipError_t launch_krylov(const KrylovArgs& a, int op, int dt_code,
 hipError_t launch_krylov_finish(const double* partials, unsigned n,
                                 double* result, double* save,
                                 hipStream_t stream);
+
+// Vertical line solves of parallel/zline.ZLineSolver (zline.hip).  T is the
+// tridiagonal matrix along z of a 3-D stencil's taps (dz, 0, 0): a below
+// the diagonal, b on it, c above, the same for every column; under
+// periodic z it also has a in its top right and c in its bottom left
+// corner.  A field is `columns` (nz, ny, nx) columns as in
+// HaloStencil3dArgs.
+//
+// `tables` is (4, nz) in the field dtype, from the host's float64 Thomas
+// factorisation rounded once:
+//   row 0  inv_k = 1 / (b_k - a cp_{k-1})            the pivots' reciprocals
+//   row 1  cp_k  = c inv_k
+//   row 2  qs_k: periodic only, q = T'^{-1} u over (1 + q_0 + g q_{nz-1})
+//   row 3  lo_k  = a for k >= 1; lo_0 = g = a / gamma (0 when not periodic)
+// where periodic z factors the Sherman-Morrison matrix T' (gamma = -b,
+// b_0' = b - gamma, b_{nz-1}' = b - a c / gamma, u = (gamma, 0, .., 0, c)).
+//
+// A thread owns one interior (j, i) column of one field and marches over
+// z; a 256-thread block owns kZlineTileY x kZlineTileX columns, lanes
+// along x.  The block index decodes, fastest first, to (tile x, tile y,
+// column, field): `blocks` = nf * columns * tiles_y * tiles_x < 2^24,
+// 32-bit; offsets into a field are 64-bit.  Per thread:
+//   forward, k = 0 .. nz-1:  y_0 = r_0 inv_0,
+//                            y_k = (r_k - lo_k y_{k-1}) inv_k
+//   back, k = nz-1 .. 0:     s_{nz-1} = y_{nz-1},  s_k = y_k - cp_k s_{k+1}
+//   periodic, k = 0 .. nz-1: z_k = s_k - qs_k (s_0 + lo_0 s_{nz-1});
+//   otherwise z_k = s_k, stored in the back sweep.
+// y_k (then s_k under periodic z) of the planes k < lds_planes is kept in
+// lds_planes * 256 * sizeof(dtype) bytes of dynamic LDS, of the other
+// planes in z[k] itself.  Only interior cells of z are written; z aliases
+// no other field.
+//
+// ZLINE_SOLVE: z = T^{-1} r.
+// ZLINE_PCG_UPDATE: the forward sweep first forms, per plane, exactly
+// KRYLOV_UPDATE's x + alpha p and rn = r - alpha q (alpha = *num / *den
+// as there), stores both, adds double(rn) * double(rn) to the thread's
+// first sum, and eliminates on rn.  The sweep that stores z_k re-reads the
+// stored rn and adds double(rn) * double(z_k) to the thread's second sum
+// (k descending, or ascending under periodic z).  Each sum goes through
+// krylov_block_sum; block `b` writes partials[b] = its r . r and
+// partials[blocks + b] = its r . z.
+constexpr int kZlineTileX = 64;
+constexpr int kZlineTileY = 4;
+constexpr int kZlineBlock = 256;
+// Dynamic LDS a block may ask for: 64 KiB less the reduction's slots.
+constexpr int kZlineMaxLds = 65536 - 64;
+
+enum ZLineMode : int {
+  ZLINE_SOLVE = 0,
+  ZLINE_PCG_UPDATE = 1,
+};
+
+struct ZLineArgs {
+  const void* p[kHaloMaxFields];  // update only
+  const void* q[kHaloMaxFields];  // update only
+  void* x[kHaloMaxFields];        // update only
+  void* r[kHaloMaxFields];        // solve: read;  update: read and written
+  void* z[kHaloMaxFields];
+  const void* tables;
+  const double* num;  // update: alpha = *num / *den, 0 when *den == 0
+  const double* den;
+  double* partials;   // update: 2 * blocks slots
+  long long ny, nx;
+  unsigned nz, columns, tiles_y, tiles_x, lds_planes;
+  int w, periodic;
+};
+
+// dt_code must be DT_F32 or DT_F64 (anything else launches nothing; the
+// caller checks), lds_planes <= nz and lds_planes * 256 * sizeof(dtype) <=
+// kZlineMaxLds.  Returns the launch's status.
+hipError_t launch_zline(const ZLineArgs& a, int mode, int dt_code,
+                        unsigned blocks, hipStream_t stream);

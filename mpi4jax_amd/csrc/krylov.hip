@@ -47,12 +47,10 @@ struct KrAcc<double> {
   using type = double;
 };
 
-// alpha or beta: the quotient in float64, 0 for a zero denominator (an
-// iteration past exact convergence changes nothing), rounded once
+// alpha or beta (krylov_quotient in krylov_reduce.h)
 template <typename Acc>
 __device__ inline Acc krylov_ratio(const KrylovArgs& a) {
-  const double den = *a.den;
-  return (Acc)(den == 0.0 ? 0.0 : *a.num / den);
+  return krylov_quotient<Acc>(a.num, a.den);
 }
 
 template <typename T, int OP>

@@ -34,3 +34,12 @@ __device__ inline double krylov_block_sum(double v) {
   }
   return s;
 }
+
+// alpha or beta of the CG kernels: *num / *den in float64, 0 for a zero
+// denominator (an iteration past exact convergence changes nothing),
+// rounded once to the accumulate type.
+template <typename Acc>
+__device__ inline Acc krylov_quotient(const double* num, const double* den) {
+  const double d = *den;
+  return (Acc)(d == 0.0 ? 0.0 : *num / d);
+}

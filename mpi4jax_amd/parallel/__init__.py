@@ -20,6 +20,10 @@ from .cg import CGInfo, StencilCG  # noqa: F401
 from . import cg  # noqa: F401
 from .chebyshev import ChebyshevInfo, StencilChebyshev  # noqa: F401
 from . import chebyshev  # noqa: F401
+from .zline import ZLineSolver  # noqa: F401
+from . import zline  # noqa: F401
+from .pcg import StencilPCG  # noqa: F401
+from . import pcg  # noqa: F401
 from .ddp import average_gradients  # noqa: F401
 from .tp import (  # noqa: F401
     ColumnParallelLinear,

@@ -73,10 +73,12 @@ class StencilCG:
 
         # halos zero, never written
         self._r, self._p, self._q = fields(), fields(), fields()
+        self._d = self._r  # what the direction step adds beta * p to
         self._x = None
         self._rs = torch.zeros((), dtype=torch.float64, device=ex.device)
         self._rs_old = torch.zeros_like(self._rs)
         self._pq = torch.zeros_like(self._rs)
+        self._res2 = self._rs  # the squared residual norm solve() tests
 
     @property
     def rs(self):
@@ -203,7 +205,7 @@ class StencilCG:
         self.start(b, x)
         if check_every == 0:
             self.iterate(maxiter)
-            return st._ret(x), CGInfo(maxiter, None, self._rs.sqrt(),
+            return st._ret(x), CGInfo(maxiter, None, self._res2.sqrt(),
                                       bb.sqrt())
         bnorm = math.sqrt(self._finite(bb, "b . b"))
         tol = max(rtol * bnorm, atol)
@@ -212,7 +214,7 @@ class StencilCG:
             n = min(check_every, maxiter - done)
             self.iterate(n)
             done += n
-            rnorm = math.sqrt(self._finite(self._rs, "r . r"))
+            rnorm = math.sqrt(self._finite(self._res2, "r . r"))
             converged = rnorm <= tol
         return st._ret(x), CGInfo(done, converged, rnorm, bnorm)
 
@@ -245,7 +247,7 @@ class StencilCG:
         from .._backend import rccl
 
         rccl.ext().halo_cg_direction_nd(
-            self._p, self._r, *self._geom(), self._rs, self._rs_old)
+            self._p, self._d, *self._geom(), self._rs, self._rs_old)
 
     def _ratio(self, num, den):
         """``num / den`` in float64, 0 where ``den == 0``, rounded once to
@@ -269,6 +271,6 @@ class StencilCG:
     def _direction_py(self):
         st = self.stencil
         beta = self._ratio(self._rs, self._rs_old)
-        for fr, fp in zip(self._r, self._p):
+        for fd, fp in zip(self._d, self._p):
             pi = st._interior(fp)
-            torch.add(st._interior(fr), beta * pi, out=pi)
+            torch.add(st._interior(fd), beta * pi, out=pi)

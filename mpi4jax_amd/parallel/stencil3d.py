@@ -20,8 +20,11 @@ With ``E`` and ``P_int`` exactly as in :mod:`.stencil`:
   ``K_t * gout[b, k - dz_t, p - (dy_t, dx_t)]`` over the taps whose source
   cell is interior and whose source plane exists; ``ex.adjoint_`` then runs
   in place;
-* ``apply_ad``, ``dot``, ``apply_dot`` and ``make_cg`` are those of
-  :class:`~.stencil.HaloStencil`.
+* ``apply_ad``, ``dot``, ``apply_dot`` and ``make_cg()`` are those of
+  :class:`~.stencil.HaloStencil`;
+* ``make_line_solver`` solves with the tridiagonal part of ``A`` along z
+  (:mod:`.zline`), and ``make_cg("zline")`` uses that as the
+  preconditioner of conjugate gradients (:mod:`.pcg`).
 
 ``z_boundary="zero"``: a tap whose source plane lies outside ``[0, nz)`` is
 not formed, so it adds nothing (an ``inf`` there makes no NaN); any
@@ -156,6 +159,31 @@ class HaloStencil3D(HaloStencil):
     def make_chebyshev(self, lmin, lmax):
         raise TypeError("make_chebyshev is 2-D only: the 3-D stencil has "
                         "no Chebyshev kernel yet")
+
+    def make_line_solver(self, _lds_planes=None):
+        """A :class:`~.zline.ZLineSolver`: ``T^{-1}`` for the tridiagonal
+        part ``T`` of this stencil along z (its ``(dz, 0, 0)`` weights).
+        ``ValueError`` for a non-zero ``(+-2, 0, 0)`` weight or a ``T``
+        whose factorisation meets a non-positive pivot; float32 and
+        float64 only (``TypeError``)."""
+        from .zline import ZLineSolver
+
+        return ZLineSolver(self, _lds_planes=_lds_planes)
+
+    def make_cg(self, preconditioner=None, _lds_planes=None):
+        """``preconditioner=None``: the :class:`~.cg.StencilCG` of
+        ``HaloStencil.make_cg``.  ``"zline"``: a
+        :class:`~.pcg.StencilPCG`, conjugate gradients preconditioned by
+        the exact vertical line solve of :meth:`make_line_solver`."""
+        if preconditioner is None:
+            return super().make_cg()
+        if preconditioner != "zline":
+            raise ValueError(
+                f"preconditioner must be None or 'zline', got "
+                f"{preconditioner!r}")
+        from .pcg import StencilPCG
+
+        return StencilPCG(self, _lds_planes=_lds_planes)
 
     # ------------------------------------------------------------------
     def _pick_z_chunk(self, forced):

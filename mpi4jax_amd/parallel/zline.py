@@ -1,0 +1,233 @@
+"""Vertical line solves for :class:`~.stencil3d.HaloStencil3D`.
+
+``T`` is the tridiagonal matrix along z made of the stencil's taps at
+``(dz, 0, 0)``: ``a`` (``dz = -1``), ``b`` (centre) and ``c`` (``dz = +1``),
+the same for every column.  Under ``z_boundary="zero"`` it is plain
+tridiagonal; under ``"periodic"`` it also has ``a`` in its top right and
+``c`` in its bottom left corner.  A :class:`ZLineSolver` (built by
+``HaloStencil3D.make_line_solver``) computes ``z = T^{-1} r`` on every
+interior column.  z is never decomposed and stores no halo, so a line solve
+needs no communication; it is the preconditioner of
+:class:`~.pcg.StencilPCG`.
+
+Tables.  ``T`` does not vary by column, so its Thomas factorisation is done
+once, on the host, in float64 and rounded once to ``Acc``:
+``inv_k = 1 / (b_k - a cp_{k-1})`` and ``cp_k = c inv_k``.  A pivot that is
+not positive and finite raises ``ValueError``.  Periodic z factors the
+Sherman-Morrison matrix ``T'`` (``gamma = -b``, ``b_0' = b - gamma``,
+``b_{nz-1}' = b - a c / gamma``) and adds ``qs = q / (1 + q_0 + g q_{nz-1})``
+with ``q = T'^{-1} (gamma, 0, .., 0, c)`` and ``g = a / gamma``.  With
+``a = c = 0`` both boundaries degenerate to a scaling by ``1 / b``.  The
+executors only multiply:
+
+* forward, ``k`` up: ``y_0 = r_0 inv_0``, ``y_k = (r_k - a y_{k-1}) inv_k``;
+* back, ``k`` down: ``s_{nz-1} = y_{nz-1}``, ``s_k = y_k - cp_k s_{k+1}``;
+* periodic only: ``z_k = s_k - qs_k (s_0 + g s_{nz-1})``; otherwise
+  ``z = s``.
+
+Executors: the native one (``csrc/zline.hip``) gives every interior
+``(j, i)`` column to one thread that marches over z.  It keeps ``y`` of the
+first ``lds_planes`` planes in LDS and of the planes above in ``z`` itself.
+The Python executor (CPU, or ``MPI4JAX_AMD_HALO_PY=1``) runs the same
+recurrences on the same tables by slicing over planes.  The native kernel
+contracts multiply and add, so the two differ by rounding except where
+every product is exact.
+
+The march is serial in z: its parallelism is the number of columns,
+``nfields * B * ny * nx``.  Very tall columns on very small horizontal
+grids leave the GPU few threads; there is no cyclic-reduction variant.
+
+float32 and float64 only.
+"""
+
+import math
+
+import torch
+
+from .cg import CG_DTYPES
+
+BLOCK = 256            # kZlineBlock of csrc/kernels.h
+TILE_Y, TILE_X = 4, 64  # kZlineTileY, kZlineTileX
+MAX_LDS = 65536 - 64   # kZlineMaxLds: 64 KiB less the reduction's slots
+
+
+def _thomas(nz, a, b, c, periodic):
+    """The four table rows as float64 lists: inv, cp, qs, lo."""
+    def bad(k, pivot):
+        return ValueError(
+            f"the stencil is not positive definite along z: pivot {k} of "
+            f"its vertical tridiagonal part is {pivot}")
+
+    diag = [b] * nz
+    gamma = -b
+    if periodic:
+        if not (math.isfinite(b) and b > 0.0):
+            raise bad(0, b)
+        diag[0], diag[-1] = b - gamma, b - a * c / gamma
+    inv, cp = [], []
+    for k in range(nz):
+        pivot = diag[k] - (a * cp[k - 1] if k else 0.0)
+        if not (math.isfinite(pivot) and pivot > 0.0):
+            raise bad(k, pivot)
+        inv.append(1.0 / pivot)
+        cp.append(c * inv[k])
+    qs, lo = [0.0] * nz, [0.0] + [a] * (nz - 1)
+    if periodic:
+        u = [gamma] + [0.0] * (nz - 2) + [c]
+        q = []
+        for k in range(nz):
+            q.append((u[k] - (a * q[k - 1] if k else 0.0)) * inv[k])
+        for k in range(nz - 2, -1, -1):
+            q[k] -= cp[k] * q[k + 1]
+        g = a / gamma
+        den = 1.0 + q[0] + g * q[-1]
+        if not (math.isfinite(den) and den > 0.0):
+            raise bad(nz, den)
+        qs, lo[0] = [v / den for v in q], g
+    return inv, cp, qs, lo
+
+
+class ZLineSolver:
+    """See the module docstring.  Build with
+    ``HaloStencil3D.make_line_solver``."""
+
+    def __init__(self, stencil, _lds_planes=None):
+        if stencil.dtype not in CG_DTYPES:
+            raise TypeError(
+                f"line solves support float32 and float64, the stencil was "
+                f"built for {stencil.dtype}")
+        band = {dz: 0.0 for dz in (-2, -1, 0, 1, 2)}
+        for dz, dy, dx, coef in stencil.taps:
+            if dy == 0 and dx == 0:
+                band[dz] = coef
+        if band[-2] != 0.0 or band[2] != 0.0:
+            raise ValueError(
+                "the stencil has a (+-2, 0, 0) weight: the tridiagonal part "
+                "of a pentadiagonal matrix need not be positive definite")
+        self.stencil = stencil
+        self._bands = a, b, c = band[-1], band[0], band[1]
+        nz = stencil.nz
+        self._periodic = (stencil.z_boundary == "periodic"
+                          and (a != 0.0 or c != 0.0))
+        ex = stencil.exchanger
+        self._tables = torch.tensor(
+            _thomas(nz, a, b, c, self._periodic), dtype=torch.float64).to(
+                stencil.acc_dtype).to(ex.device)
+        most = MAX_LDS // (BLOCK * ex.dtype.itemsize)
+        if _lds_planes is None:
+            _lds_planes = min(nz, most)
+        elif (isinstance(_lds_planes, bool)
+              or not isinstance(_lds_planes, int)
+              or not 0 <= _lds_planes <= min(nz, most)):
+            raise ValueError(
+                f"_lds_planes must be an int in 0..{min(nz, most)}, got "
+                f"{_lds_planes!r}")
+        self._lds_planes = _lds_planes
+        self._partials = None
+
+    @property
+    def bands(self):
+        """``(a, b, c)``: the weights at ``dz = -1, 0, +1``."""
+        return self._bands
+
+    @property
+    def lds_planes(self):
+        """Planes of the forward sweep that the native kernel keeps in
+        LDS; the planes above go through the output array."""
+        return self._lds_planes
+
+    @property
+    def tables(self):
+        """The ``(4, nz)`` device tensor of ``inv``, ``cp``, ``qs`` and
+        ``lo`` in ``Acc`` (``lo[0]`` holds ``g``)."""
+        return self._tables
+
+    def solve(self, *fields, out=None):
+        """``T^{-1}`` on the interior columns of ``fields``; the inputs
+        are never mutated.  Results and ``out=`` as in
+        ``HaloStencil.apply``: new tensors have a zero halo, and only the
+        interior of ``out`` is written."""
+        st = self.stencil
+        st.exchanger._check(fields)
+        outs = st._outputs(fields, out, zero=True)
+        self._solve_into(fields, outs)
+        return st._ret(outs)
+
+    # ------------------------------------------------------------------
+    def _geom(self):
+        st = self.stencil
+        ex = st.exchanger
+        return (ex.levels, st.nz, ex.ny, ex.nx, st.width, self._tables,
+                self._periodic, self._lds_planes)
+
+    def _partials_buf(self):
+        """Two float64 slots per block of the native kernel's grid."""
+        if self._partials is None:
+            st = self.stencil
+            ex = st.exchanger
+            w = st.width
+            tiles = (-(-(ex.ny - 2 * w) // TILE_Y)
+                     * -(-(ex.nx - 2 * w) // TILE_X))
+            self._partials = torch.empty(
+                2 * ex.nfields * (ex.levels // st.nz) * tiles,
+                dtype=torch.float64, device=ex.device)
+        return self._partials
+
+    def _solve_into(self, rs, zs):
+        if self.stencil._native():
+            from .._backend import rccl
+
+            rccl.ext().halo_zline_solve_nd(list(rs), list(zs), *self._geom())
+        else:
+            for r, z in zip(rs, zs):
+                self._columns(z).copy_(self._solve_py(self._columns(r)))
+
+    def _columns(self, t):
+        """The interior of ``t`` as ``(B, nz, ny - 2w, nx - 2w)``."""
+        st = self.stencil
+        ex = st.exchanger
+        w = st.width
+        return t.view(-1, st.nz, ex.ny, ex.nx)[:, :, w:ex.ny - w,
+                                               w:ex.nx - w]
+
+    def _solve_py(self, r):
+        nz = self.stencil.nz
+        inv, cp, qs, lo = self._tables
+        y = torch.empty_like(r)
+        y[:, 0] = r[:, 0] * inv[0]
+        for k in range(1, nz):
+            y[:, k] = (r[:, k] - lo[k] * y[:, k - 1]) * inv[k]
+        for k in range(nz - 2, -1, -1):
+            y[:, k] -= cp[k] * y[:, k + 1]
+        if self._periodic:
+            fac = y[:, 0] + lo[0] * y[:, nz - 1]
+            y -= qs[:, None, None] * fac[:, None]
+        return y
+
+    def _pcg_update(self, x, r, p, q, z, rz, pq, rz_old, rr):
+        """The update step of :class:`~.pcg.StencilPCG` on this rank:
+        ``alpha = rz / pq``; ``x += alpha p``; ``r -= alpha q``;
+        ``z = T^{-1} r``; ``rr = r . r``; ``rz_old = rz``;
+        ``rz = r . z``."""
+        st = self.stencil
+        if st._native():
+            from .._backend import rccl
+
+            rccl.ext().halo_zline_pcg_update_nd(
+                x, r, p, q, z, *self._geom(), rz, pq, rz_old, rr,
+                self._partials_buf())
+            return
+        alpha = torch.where(pq == 0, torch.zeros_like(rz), rz / pq).to(
+            st.acc_dtype)
+        sum_rr = sum_rz = 0.0
+        for fx, fr, fp, fq, fz in zip(x, r, p, q, z):
+            st._interior(fx).add_(alpha * st._interior(fp))
+            ri = self._columns(fr)
+            ri.sub_(alpha * self._columns(fq))
+            zi = self._columns(fz)
+            zi.copy_(self._solve_py(ri))
+            sum_rr = sum_rr + (ri.double() * ri.double()).sum()
+            sum_rz = sum_rz + (ri.double() * zi.double()).sum()
+        rz_old.copy_(rz)
+        rz.copy_(sum_rz)
+        rr.copy_(sum_rr)
