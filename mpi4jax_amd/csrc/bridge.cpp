@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <deque>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -941,22 +942,31 @@ struct HaloNdPlan {
   void* fptr[kHaloMaxFields];
 };
 
+// What every halo entry takes after its fields, as the entry got it.
+struct HaloCall {
+  int64_t levels, ny, nx, width;
+  const std::vector<int64_t>& send_to;
+  const std::vector<int64_t>& recv_from;
+  int64_t local_mask;
+  const at::Tensor& sbuf;
+  const at::Tensor& rbuf;
+  int64_t comm_id;
+};
+
 // Argument checks and slot geometry shared by halo_exchange_nd and
 // halo_adjoint_nd (`who` names the entry in the one message that does).
 HaloNdPlan halo_nd_plan(const char* who,
                         const std::vector<at::Tensor>& fields,
-                        int64_t levels, int64_t ny, int64_t nx,
-                        int64_t width, const std::vector<int64_t>& send_to,
-                        const std::vector<int64_t>& recv_from,
-                        int64_t local_mask, const at::Tensor& sbuf,
-                        const at::Tensor& rbuf) {
+                        const HaloCall& x) {
+  const int64_t levels = x.levels, ny = x.ny, nx = x.nx;
+  const std::vector<int64_t>&send_to = x.send_to, &recv_from = x.recv_from;
   HaloNdPlan p{};
   const int64_t nf = (int64_t)fields.size();
   TORCH_CHECK(1 <= nf && nf <= kHaloMaxFields, "1..", kHaloMaxFields,
               " halo fields supported, got ", nf);
   TORCH_CHECK(send_to.size() == kHaloDirs && recv_from.size() == kHaloDirs,
               who, " expects 8 send and 8 recv peers");
-  const int64_t w = width;
+  const int64_t w = x.width;
   TORCH_CHECK(w >= 1 && levels >= 1 && ny >= 3 * w && nx >= 3 * w,
               "bad halo geometry: levels ", levels, ", ny ", ny, ", nx ", nx,
               ", width ", w, " (each axis needs n >= 3*width)");
@@ -986,19 +996,19 @@ HaloNdPlan halo_nd_plan(const char* who,
   const int64_t total = p.g.total;
   TORCH_CHECK(total < ((int64_t)1 << 31),
               "halo staging of ", total, " elements exceeds 2^31");
-  for (const at::Tensor* b : {&sbuf, &rbuf}) {
+  for (const at::Tensor* b : {&x.sbuf, &x.rbuf}) {
     TORCH_CHECK(b->is_cuda() && b->is_contiguous() &&
                     b->device() == f0.device() &&
                     b->element_size() == esz && b->numel() >= total,
                 "bad halo staging buffer (need ", total, " elements of ",
                 esz, " bytes on the fields' device)");
   }
-  TORCH_CHECK(0 <= local_mask && local_mask < (1 << kHaloDirs),
+  TORCH_CHECK(0 <= x.local_mask && x.local_mask < (1 << kHaloDirs),
               "bad halo local mask");
 
   for (int i = 0; i < kHaloDirs; ++i) {
     TORCH_CHECK(send_to[i] >= -1 && recv_from[i] >= -1, "bad halo peer");
-    if ((local_mask >> i) & 1) {
+    if ((x.local_mask >> i) & 1) {
       TORCH_CHECK(send_to[i] >= 0 && recv_from[i] >= 0,
                   "local halo entry ", i, " needs both peers");
     } else {
@@ -1027,23 +1037,94 @@ HaloNdPlan halo_nd_plan(const char* who,
 // of the RECEIVE buffer and never enters the group.  Messages travel as
 // raw bytes, so any dtype of a supported element size is exchanged.
 //
-// halo_exchange_send is the part halo_stencil_nd shares: the pack launch
-// and the RCCL group.  The caller enqueues what consumes the receive slots
-// (halo_exchange_nd its unpack launch, built here as `un`; halo_stencil_nd
-// its own kernel) and arms the watchdog when `rank` >= 0.
+// halo_exchange_send is the part the stencil entries share: the pack
+// launch and the RCCL group.  The caller enqueues what consumes the receive
+// slots (halo_exchange_nd its unpack launch, built here as `un`; a stencil
+// entry its own kernel) and arms the watchdog when `rank` >= 0.
 
 // The communicator of a call with a remote entry, its peers checked
-// against the communicator's size.  False when nothing is remote.
-bool halo_peers(const HaloNdPlan& plan, int64_t comm_id,
-                const std::vector<int64_t>& send_to,
-                const std::vector<int64_t>& recv_from, CommEntry* c) {
-  if (!plan.any_remote) return false;
-  *c = get_comm(comm_id);
+// against the communicator's size.  Empty when nothing is remote.  Every
+// entry calls this once, before its first launch.
+std::optional<CommEntry> halo_peers(const HaloNdPlan& plan,
+                                    const HaloCall& x) {
+  if (!plan.any_remote) return std::nullopt;
+  const CommEntry c = get_comm(x.comm_id);
   for (int i = 0; i < kHaloDirs; ++i) {
-    TORCH_CHECK(send_to[i] < c->size && recv_from[i] < c->size,
-                "halo peer out of range for communicator of size ", c->size);
+    TORCH_CHECK(x.send_to[i] < c.size && x.recv_from[i] < c.size,
+                "halo peer out of range for communicator of size ", c.size);
   }
-  return true;
+  return c;
+}
+
+// The arguments of one launch_halo_nd over the fields `f`: a segment, in
+// entry order, for every entry i with peer[i] >= 0, on slot i of `buf`
+// (of `local_buf` when the entry is local).  `recv` picks the entry's
+// receive window, else its send window.
+HaloNdArgs halo_nd_segments(const HaloNdPlan& plan, void* const* f,
+                            const HaloCall& x,
+                            const std::vector<int64_t>& peer, bool recv,
+                            char* buf, char* local_buf) {
+  const HaloGeom& g = plan.g;
+  HaloNdArgs a{};
+  for (int64_t k = 0; k < plan.nf; ++k) a.f[k] = f[k];
+  a.ny = x.ny;
+  a.nx = x.nx;
+  a.levels = (unsigned)x.levels;
+  a.nf = (int)plan.nf;
+  a.w = (int)plan.w;
+  int n = 0;
+  unsigned pos = 0;
+  for (int i = 0; i < kHaloDirs; ++i) {
+    if (peer[i] < 0) continue;
+    HaloNdSeg& s = a.seg[n++];
+    s.buf = (((x.local_mask >> i) & 1) ? local_buf : buf) +
+            g.slot_off[i] * plan.esz;
+    s.y0 = recv ? g.ry[i] : g.sy[i];
+    s.x0 = recv ? g.rx[i] : g.sx[i];
+    s.h = (unsigned)g.hh[i];
+    s.wd = (unsigned)g.ww[i];
+    s.start = pos;
+    pos += (unsigned)(g.slot_off[i + 1] - g.slot_off[i]);
+    s.end = pos;
+    s.skip_lo = s.skip_hi = 0;
+    if (recv && i < 2) {
+      // column strip with x-direction dx: its low rows [0, w) are the
+      // receive block of diagonal (+1, dx), its high rows of (-1, dx);
+      // a present corner segment owns them ("corners win")
+      const int lo = i == 0 ? 6 : 7, hi = i == 0 ? 4 : 5;
+      s.skip_lo = peer[lo] >= 0;
+      s.skip_hi = peer[hi] >= 0;
+    }
+  }
+  a.total = pos;
+  for (int i = n; i < kHaloDirs; ++i) a.seg[i].end = a.total;
+  return a;
+}
+
+// One RCCL group on `stream` over the entries that are not local: slot i
+// of `sb` is sent to to[i] and slot i of `rb` received from from[i], in
+// entry order, so message i pairs with message i on both sides.
+void halo_group(const char* log_name, const CommEntry& c,
+                const HaloNdPlan& plan, int64_t local_mask,
+                const std::vector<int64_t>& to,
+                const std::vector<int64_t>& from, char* sb, char* rb,
+                hipStream_t stream) {
+  const int64_t* off = plan.g.slot_off;
+  log_enqueue(log_name, c, plan.total);
+  RCCL_CHECK(ncclGroupStart());
+  for (int i = 0; i < kHaloDirs; ++i) {
+    if ((local_mask >> i) & 1) continue;
+    const int64_t nbytes = (off[i + 1] - off[i]) * plan.esz;
+    if (to[i] >= 0) {
+      p2p_send(sb + off[i] * plan.esz, nbytes, ncclUint8, 1, (int)to[i],
+               c.comm, stream);
+    }
+    if (from[i] >= 0) {
+      p2p_recv(rb + off[i] * plan.esz, nbytes, ncclUint8, 1, (int)from[i],
+               c.comm, stream);
+    }
+  }
+  RCCL_CHECK(ncclGroupEnd());
 }
 
 struct HaloNdSent {
@@ -1052,90 +1133,23 @@ struct HaloNdSent {
   int rank;  // of this process in the group's communicator; -1: no group
 };
 
+// `comm` is what halo_peers returned for this call.
 HaloNdSent halo_exchange_send(const char* log_name, const HaloNdPlan& plan,
-                              int64_t levels, int64_t ny, int64_t nx,
-                              const std::vector<int64_t>& send_to,
-                              const std::vector<int64_t>& recv_from,
-                              int64_t local_mask, const at::Tensor& sbuf,
-                              const at::Tensor& rbuf, int64_t comm_id) {
-  const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
-  const int64_t total = plan.total;
-  const int64_t* slot_off = plan.g.slot_off;
-  const int64_t *sy = plan.g.sy, *sx = plan.g.sx, *ry = plan.g.ry,
-                *rx = plan.g.rx, *hh = plan.g.hh, *ww = plan.g.ww;
-  auto is_local = [&](int i) { return (local_mask >> i) & 1; };
-  HaloNdArgs pk{}, un{};
-  for (int64_t k = 0; k < nf; ++k) pk.f[k] = un.f[k] = plan.fptr[k];
-
-  char* sb = (char*)sbuf.data_ptr();
-  char* rb = (char*)rbuf.data_ptr();
-  auto fill_common = [&](HaloNdArgs& a) {
-    a.ny = ny;
-    a.nx = nx;
-    a.levels = (unsigned)levels;
-    a.nf = (int)nf;
-    a.w = (int)w;
-  };
-  fill_common(pk);
-  fill_common(un);
-  auto add_seg = [&](HaloNdArgs& a, int& n, unsigned& pos, int i, char* base,
-                     int64_t y0, int64_t x0) {
-    HaloNdSeg& s = a.seg[n++];
-    s.buf = base + slot_off[i] * esz;
-    s.y0 = y0;
-    s.x0 = x0;
-    s.h = (unsigned)hh[i];
-    s.wd = (unsigned)ww[i];
-    s.start = pos;
-    pos += (unsigned)(slot_off[i + 1] - slot_off[i]);
-    s.end = pos;
-    s.skip_lo = s.skip_hi = 0;
-  };
-  int npk = 0, nun = 0;
-  unsigned pk_pos = 0, un_pos = 0;
-  for (int i = 0; i < kHaloDirs; ++i) {
-    if (send_to[i] >= 0) {
-      add_seg(pk, npk, pk_pos, i, is_local(i) ? rb : sb, sy[i], sx[i]);
-    }
-    if (recv_from[i] >= 0) {
-      add_seg(un, nun, un_pos, i, rb, ry[i], rx[i]);
-      if (i < 2) {
-        // column strip with x-direction dx: its low rows [0, w) are the
-        // receive block of diagonal (+1, dx), its high rows of (-1, dx);
-        // a present corner segment owns them ("corners win")
-        const int lo = i == 0 ? 6 : 7, hi = i == 0 ? 4 : 5;
-        un.seg[nun - 1].skip_lo = recv_from[lo] >= 0;
-        un.seg[nun - 1].skip_hi = recv_from[hi] >= 0;
-      }
-    }
+                              const HaloCall& x,
+                              const std::optional<CommEntry>& comm) {
+  char* sb = (char*)x.sbuf.data_ptr();
+  char* rb = (char*)x.rbuf.data_ptr();
+  const HaloNdArgs pk =
+      halo_nd_segments(plan, plan.fptr, x, x.send_to, false, sb, rb);
+  const HaloNdSent sent{
+      halo_nd_segments(plan, plan.fptr, x, x.recv_from, true, rb, rb),
+      cur_stream(), comm ? comm->rank : -1};
+  launch_halo_nd(pk, 0, (int)plan.esz, sent.stream);
+  if (comm) {
+    halo_group(log_name, *comm, plan, x.local_mask, x.send_to, x.recv_from,
+               sb, rb, sent.stream);
   }
-  pk.total = pk_pos;
-  un.total = un_pos;
-  for (int i = npk; i < kHaloDirs; ++i) pk.seg[i].end = pk.total;
-  for (int i = nun; i < kHaloDirs; ++i) un.seg[i].end = un.total;
-
-  CommEntry c{};
-  const bool remote = halo_peers(plan, comm_id, send_to, recv_from, &c);
-  hipStream_t stream = cur_stream();
-  launch_halo_nd(pk, 0, (int)esz, stream);
-  if (remote) {
-    log_enqueue(log_name, c, total);
-    RCCL_CHECK(ncclGroupStart());
-    for (int i = 0; i < kHaloDirs; ++i) {
-      if (is_local(i)) continue;
-      const int64_t nbytes = (slot_off[i + 1] - slot_off[i]) * esz;
-      if (send_to[i] >= 0) {
-        p2p_send(sb + slot_off[i] * esz, nbytes, ncclUint8, 1,
-                 (int)send_to[i], c.comm, stream);
-      }
-      if (recv_from[i] >= 0) {
-        p2p_recv(rb + slot_off[i] * esz, nbytes, ncclUint8, 1,
-                 (int)recv_from[i], c.comm, stream);
-      }
-    }
-    RCCL_CHECK(ncclGroupEnd());
-  }
-  return HaloNdSent{un, stream, remote ? c.rank : -1};
+  return sent;
 }
 
 void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
@@ -1144,32 +1158,29 @@ void halo_exchange_nd(std::vector<at::Tensor> fields, int64_t levels,
                       std::vector<int64_t> recv_from, int64_t local_mask,
                       at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_exchange_nd");
-  const HaloNdPlan plan =
-      halo_nd_plan("halo_exchange_nd", fields, levels, ny, nx, width,
-                   send_to, recv_from, local_mask, sbuf, rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan("halo_exchange_nd", fields, x);
   const HaloNdSent sent =
-      halo_exchange_send("HaloExchangeNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
+      halo_exchange_send("HaloExchangeNd", plan, x, halo_peers(plan, x));
   launch_halo_nd(sent.un, 1, (int)plan.esz, sent.stream);
   if (sent.rank >= 0) watchdog_arm("halo_exchange_nd", sent.rank, sent.stream);
 }
 
-// The checks halo_adjoint_nd adds to halo_nd_plan's, shared with
-// halo_stencil_adjoint_nd, which must pass them before its first launch.
+// The checks halo_adjoint_nd adds to halo_nd_plan's, shared with the
+// stencil adjoints, which must pass them before their first launch.
 HaloFrame halo_adjoint_checks(const HaloNdPlan& plan,
                               const std::vector<at::Tensor>& fields,
-                              int64_t levels, int64_t ny, int64_t nx,
-                              const at::Tensor& sbuf,
-                              const at::Tensor& rbuf) {
+                              const HaloCall& x) {
   const auto st = fields[0].scalar_type();
   TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kHalf ||
                   st == at::kBFloat16,
               "halo adjoint supports float16, bfloat16, float32 and "
               "float64, got ", st);
-  TORCH_CHECK(sbuf.scalar_type() == st && rbuf.scalar_type() == st,
+  TORCH_CHECK(x.sbuf.scalar_type() == st && x.rbuf.scalar_type() == st,
               "halo adjoint staging buffers must have the fields' dtype");
-  const HaloFrame fr = halo_frame(ny, nx, plan.w);
-  const int64_t work = plan.nf * levels * fr.per_level;
+  const HaloFrame fr = halo_frame(x.ny, x.nx, plan.w);
+  const int64_t work = plan.nf * x.levels * fr.per_level;
   TORCH_CHECK_VALUE(work < ((int64_t)1 << 31), "halo adjoint over ", work,
                     " frame cells exceeds the 2^31 work-item limit");
   return fr;
@@ -1192,118 +1203,145 @@ HaloFrame halo_adjoint_checks(const HaloNdPlan& plan,
 //      window of entry i.  Send windows overlap, so the kernel works per
 //      field cell and gathers that cell's terms, last entry first.
 // Floating dtypes only: step 3 is arithmetic.
-void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
-                     int64_t ny, int64_t nx, int64_t width,
-                     std::vector<int64_t> send_to,
-                     std::vector<int64_t> recv_from, int64_t local_mask,
-                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
-  ROCTX_SCOPE("mpi4jax_amd::halo_adjoint_nd");
-  const HaloNdPlan plan =
-      halo_nd_plan("halo_adjoint_nd", fields, levels, ny, nx, width,
-                   send_to, recv_from, local_mask, sbuf, rbuf);
-  const int64_t nf = plan.nf, w = plan.w, esz = plan.esz;
+//
+// halo_adjoint_run enqueues the three steps on `fields`, which have the
+// shape, dtype and device of the fields that `plan` and `fr` were checked
+// on; `comm` is what halo_peers returned.  It checks nothing.
+void halo_adjoint_run(const HaloNdPlan& plan, const HaloFrame& fr,
+                      const std::vector<at::Tensor>& fields,
+                      const HaloCall& x,
+                      const std::optional<CommEntry>& comm) {
   const HaloGeom& g = plan.g;
-  const HaloFrame fr =
-      halo_adjoint_checks(plan, fields, levels, ny, nx, sbuf, rbuf);
-  const int64_t work = nf * levels * fr.per_level;
-  auto is_local = [&](int i) { return (local_mask >> i) & 1; };
-
-  char* sb = (char*)sbuf.data_ptr();
-  char* rb = (char*)rbuf.data_ptr();
-  HaloNdArgs pk{};
+  char* sb = (char*)x.sbuf.data_ptr();
+  char* rb = (char*)x.rbuf.data_ptr();
   HaloAdjArgs ac{};
-  for (int64_t k = 0; k < nf; ++k) pk.f[k] = ac.f[k] = plan.fptr[k];
-  pk.ny = ac.ny = ny;
-  pk.nx = ac.nx = nx;
-  pk.levels = ac.levels = (unsigned)levels;
-  pk.nf = ac.nf = (int)nf;
-  pk.w = ac.w = (int)w;
-  int npk = 0;
-  unsigned pos = 0;
+  for (int64_t k = 0; k < plan.nf; ++k) ac.f[k] = fields[k].data_ptr();
+  ac.ny = x.ny;
+  ac.nx = x.nx;
+  ac.levels = (unsigned)x.levels;
+  ac.nf = (int)plan.nf;
+  ac.w = (int)plan.w;
   for (int i = 0; i < kHaloDirs; ++i) {
-    const int64_t n = g.slot_off[i + 1] - g.slot_off[i];
-    if (recv_from[i] >= 0) {
-      HaloNdSeg& s = pk.seg[npk++];
-      s.buf = (is_local(i) ? rb : sb) + g.slot_off[i] * esz;
-      s.y0 = g.ry[i];
-      s.x0 = g.rx[i];
-      s.h = (unsigned)g.hh[i];
-      s.wd = (unsigned)g.ww[i];
-      s.start = pos;
-      pos += (unsigned)n;
-      s.end = pos;
-      s.skip_lo = s.skip_hi = 0;
-      if (i < 2) {  // as in halo_exchange_nd's unpack: corners won
-        const int lo = i == 0 ? 6 : 7, hi = i == 0 ? 4 : 5;
-        s.skip_lo = recv_from[lo] >= 0;
-        s.skip_hi = recv_from[hi] >= 0;
-      }
-    }
     HaloAdjSeg& a = ac.seg[i];
-    a.buf = rb + g.slot_off[i] * esz;
+    a.buf = rb + g.slot_off[i] * plan.esz;
     a.sy = (int)g.sy[i];
     a.sx = (int)g.sx[i];
     a.ry = (int)g.ry[i];
     a.rx = (int)g.rx[i];
     a.h = (unsigned)g.hh[i];
     a.wd = (unsigned)g.ww[i];
-    a.acc = send_to[i] >= 0;
-    a.zero = recv_from[i] >= 0;
+    a.acc = x.send_to[i] >= 0;
+    a.zero = x.recv_from[i] >= 0;
   }
-  pk.total = pos;
-  for (int i = npk; i < kHaloDirs; ++i) pk.seg[i].end = pk.total;
   ac.full = fr.full;
   ac.band = fr.full ? 0u : (unsigned)fr.band;  // 2 * band <= per_level
   ac.per_level = (unsigned)fr.per_level;
-  ac.total = (unsigned)work;
+  ac.total = (unsigned)(plan.nf * x.levels * fr.per_level);
+  const HaloNdArgs pk =
+      halo_nd_segments(plan, ac.f, x, x.recv_from, true, sb, rb);
 
-  CommEntry c{};
-  const bool remote = halo_peers(plan, comm_id, send_to, recv_from, &c);
   hipStream_t stream = cur_stream();
-  launch_halo_nd(pk, 2, (int)esz, stream);
-
-  if (remote) {
-    log_enqueue("HaloAdjointNd", c, plan.total);
-    RCCL_CHECK(ncclGroupStart());
-    for (int i = 0; i < kHaloDirs; ++i) {
-      if (is_local(i)) continue;
-      const int64_t nbytes = (g.slot_off[i + 1] - g.slot_off[i]) * esz;
-      if (recv_from[i] >= 0) {
-        p2p_send(sb + g.slot_off[i] * esz, nbytes, ncclUint8, 1,
-                 (int)recv_from[i], c.comm, stream);
-      }
-      if (send_to[i] >= 0) {
-        p2p_recv(rb + g.slot_off[i] * esz, nbytes, ncclUint8, 1,
-                 (int)send_to[i], c.comm, stream);
-      }
-    }
-    RCCL_CHECK(ncclGroupEnd());
-    launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
-    watchdog_arm("halo_adjoint_nd", c.rank, stream);
-  } else {
-    launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
+  launch_halo_nd(pk, 2, (int)plan.esz, stream);
+  if (comm) {
+    halo_group("HaloAdjointNd", *comm, plan, x.local_mask, x.recv_from,
+               x.send_to, sb, rb, stream);
   }
+  launch_halo_adjoint_acc(ac, dt_code(fields[0]), stream);
+  if (comm) watchdog_arm("halo_adjoint_nd", comm->rank, stream);
+}
+
+void halo_adjoint_nd(std::vector<at::Tensor> fields, int64_t levels,
+                     int64_t ny, int64_t nx, int64_t width,
+                     std::vector<int64_t> send_to,
+                     std::vector<int64_t> recv_from, int64_t local_mask,
+                     at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_adjoint_nd");
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan("halo_adjoint_nd", fields, x);
+  const HaloFrame fr = halo_adjoint_checks(plan, fields, x);
+  halo_adjoint_run(plan, fr, fields, x, halo_peers(plan, x));
 }
 
 // ---- fused halo stencil (parallel/stencil.HaloStencil, stencil.hip)
 
-// Checks of both stencil entries beyond halo_nd_plan's on `fields`, and
-// the kernel arguments that do not depend on the mode.  Raises before
-// anything is enqueued.
-HaloStencilArgs halo_stencil_args(const char* who, const HaloNdPlan& plan,
-                                  const std::vector<at::Tensor>& fields,
-                                  const std::vector<at::Tensor>& outs,
-                                  int64_t levels, int64_t ny, int64_t nx,
-                                  const std::vector<int64_t>& tap_dy,
-                                  const std::vector<int64_t>& tap_dx,
-                                  const std::vector<double>& tap_coef,
-                                  bool transposed, unsigned* blocks) {
+// The launch sequence of the apply, dot and Chebyshev entries of every
+// stencil family, after all of the entry's own checks.  `launch` enqueues
+// the entry's kernels on the stream it is given and returns their status.
+//   * No remote entry (direct path): `launch` alone.  A received cell is
+//     read from the input field at the entry's send window, so the staging
+//     buffers are not touched and no communicator is looked up.
+//   * Otherwise (staged path): halo_exchange_nd's pack launch and RCCL
+//     group, then `launch`, whose kernel reads received cells from the
+//     receive slots instead of unpacking them.
+template <typename Launch>
+void halo_stencil_sequence(const char* who, const char* log_name,
+                           const HaloNdPlan& plan, const HaloCall& x,
+                           Launch launch) {
+  const std::optional<CommEntry> comm = halo_peers(plan, x);
+  if (!comm) {
+    HIP_CHECK(launch(cur_stream()));
+    return;
+  }
+  const HaloNdSent sent = halo_exchange_send(log_name, plan, x, comm);
+  HIP_CHECK(launch(sent.stream));
+  watchdog_arm(who, sent.rank, sent.stream);
+}
+
+// The launch sequence of the three adjoint entries: gins = E^T . S^T .
+// P_int (gouts).  `launch` is one launch of the family's transposed mode,
+// which writes every cell of `gins`; the halo adjoint then runs in place
+// on them.  Everything it needs is checked before the launch.
+template <typename Launch>
+void halo_stencil_adjoint_sequence(const HaloNdPlan& plan,
+                                   const std::vector<at::Tensor>& gouts,
+                                   const std::vector<at::Tensor>& gins,
+                                   const HaloCall& x, Launch launch) {
+  const HaloFrame fr = halo_adjoint_checks(plan, gouts, x);
+  const std::optional<CommEntry> comm = halo_peers(plan, x);
+  HIP_CHECK(launch(cur_stream()));
+  ROCTX_SCOPE("mpi4jax_amd::halo_adjoint_nd");
+  halo_adjoint_run(plan, fr, gins, x, comm);
+}
+
+struct TileGrid {
+  unsigned tiles_y, tiles_x, blocks;  // blocks = groups * tiles_y * tiles_x
+};
+
+// `groups` grids of tile_y x tile_x tiles over the cells of a (ny, nx)
+// plane that lie `org` or more from every edge.  HIP refuses a launch of
+// 2^32 threads or more: 256-thread blocks, so fewer than 2^24 of them.
+// `noun` says what a group is in the message.
+TileGrid tile_grid(const char* who, int64_t ny, int64_t nx, int64_t org,
+                   int64_t tile_y, int64_t tile_x, int64_t groups,
+                   const char* noun) {
+  static_assert(kZlineBlock == kStencilBlock, "one launch limit for all");
+  const int64_t tiles_y = (ny - 2 * org + tile_y - 1) / tile_y;
+  const int64_t tiles_x = (nx - 2 * org + tile_x - 1) / tile_x;
+  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
+  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
+                        groups * (tiles_y * tiles_x) < max_blocks,
+                    who, ": ", groups, " ", noun, " of ", tiles_y, " x ",
+                    tiles_x, " tiles exceed the launch limit of 2^24 blocks");
+  return TileGrid{(unsigned)tiles_y, (unsigned)tiles_x,
+                  (unsigned)(groups * tiles_y * tiles_x)};
+}
+
+// The checks every stencil family makes beyond halo_nd_plan's on `fields`:
+// the width, the in-plane tap offsets (`ncoef` is the length of the
+// family's coefficient list), the dtype, the outputs and their address
+// ranges.  Raises before anything is enqueued.
+void halo_stencil_checks(const char* who, const HaloNdPlan& plan,
+                         const std::vector<at::Tensor>& fields,
+                         const std::vector<at::Tensor>& outs,
+                         const std::vector<int64_t>& tap_dy,
+                         const std::vector<int64_t>& tap_dx, size_t ncoef) {
   const int64_t nf = plan.nf, w = plan.w;
   TORCH_CHECK(w <= kStencilMaxWidth, who, ": stencil width ", w,
               " exceeds ", kStencilMaxWidth);
   const size_t nt = tap_dy.size();
   TORCH_CHECK(nt >= 1 && nt <= (size_t)kStencilMaxTaps &&
-                  tap_dx.size() == nt && tap_coef.size() == nt,
+                  tap_dx.size() == nt && ncoef == nt,
               who, ": the three tap lists must have one length in 1..",
               kStencilMaxTaps);
   for (size_t t = 0; t < nt; ++t) {
@@ -1341,77 +1379,29 @@ HaloStencilArgs halo_stencil_args(const char* who, const HaloNdPlan& plan,
       }
     }
   }
-  const int64_t org = transposed ? 0 : w;
-  const int64_t tiles_y = (ny - 2 * org + kStencilTileY - 1) / kStencilTileY;
-  const int64_t tiles_x = (nx - 2 * org + kStencilTileX - 1) / kStencilTileX;
-  // HIP refuses a launch of 2^32 threads or more: 256-thread blocks, so
-  // fewer than 2^24 of them
-  const int64_t planes = nf * levels;  // < 2^34
-  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
-  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
-                        planes * (tiles_y * tiles_x) < max_blocks,
-                    who, ": ", planes, " planes of ", tiles_y, " x ", tiles_x,
-                    " tiles exceed the launch limit of 2^24 blocks");
-  *blocks = (unsigned)(planes * tiles_y * tiles_x);
-
-  HaloStencilArgs a{};
-  for (int64_t k = 0; k < nf; ++k) {
-    a.in[k] = fields[k].data_ptr();
-    a.out[k] = outs[k].data_ptr();
-  }
-  const int64_t stride = kStencilTileX + 2 * w;
-  for (size_t t = 0; t < nt; ++t) {
-    if (st == at::kDouble) {
-      a.coef.f64[t] = tap_coef[t];
-    } else {
-      a.coef.f32[t] = (float)tap_coef[t];
-    }
-    const int64_t off = tap_dy[t] * stride + tap_dx[t];
-    a.tap_off[t] = (int)(transposed ? -off : off);
-  }
-  a.ny = ny;
-  a.nx = nx;
-  a.levels = (unsigned)levels;
-  a.tiles_y = (unsigned)tiles_y;
-  a.tiles_x = (unsigned)tiles_x;
-  a.w = (int)w;
-  a.ntaps = (int)nt;
-  return a;
 }
 
-// Native executor of HaloStencil.apply: outs = P_int . S . E (fields),
-// the fields themselves never written.  Arguments as halo_exchange_nd,
-// plus the outputs and the taps (dy, dx, coefficient) in the order they
-// are added.
-//
-// Where the exchange would have written halo cell (y, x) from, by region
-// (low halo, interior, high halo) along y and x: a side region from its
-// column or row entry, a corner region from its corner entry or else from
-// the column entry on its side ("corners win"), and from itself when that
-// entry has no sender.
-//   * No remote entry (direct path): ONE launch.  A received cell is read
-//     from the input field at the entry's send window, so the staging
-//     buffers are not touched and no communicator is looked up.
-//   * Otherwise (staged path): halo_exchange_nd's pack launch and RCCL
-//     group, then ONE stencil launch that reads received cells from the
-//     receive slots instead of unpacking them.
-// The region table of mode 0: where each of the nine regions of a plane
-// reads its cells from (see above).
-void halo_stencil_regions(HaloStencilArgs& a, const HaloNdPlan& plan,
-                          const std::vector<int64_t>& recv_from,
-                          const at::Tensor& rbuf, int64_t nx) {
+// The region table of mode 0: where the exchange would have written halo
+// cell (y, x) from, by region (low halo, interior, high halo) along y and
+// x: a side region from its column or row entry, a corner region from its
+// corner entry or else from the column entry on its side ("corners win"),
+// and from itself when that entry has no sender.  On the direct path that
+// is the input field at the entry's send window, on the staged path the
+// entry's receive slot.
+void halo_stencil_regions(StencilRegion (&reg)[9], const HaloNdPlan& plan,
+                          const HaloCall& x) {
   const HaloGeom& g = plan.g;
-  const char* rb = (const char*)rbuf.data_ptr();
+  const char* rb = (const char*)x.rbuf.data_ptr();
   // entry of region [ky][kx]; for a corner, the corner entry and then the
   // column entry that covers it
   static const int first[9] = {7, 2, 6, 1, -1, 0, 5, 3, 4};
   static const int second[9] = {1, -1, 0, -1, -1, -1, 1, -1, 0};
   for (int k = 0; k < 9; ++k) {
-    StencilRegion& r = a.reg[k];
+    StencilRegion& r = reg[k];
     r.kind = STENCIL_OWN;
     int e = first[k];
-    if (e >= 0 && recv_from[e] < 0) e = second[k];
-    if (e < 0 || recv_from[e] < 0) continue;
+    if (e >= 0 && x.recv_from[e] < 0) e = second[k];
+    if (e < 0 || x.recv_from[e] < 0) continue;
     if (plan.any_remote) {
       r.kind = STENCIL_SLOT;
       r.buf = rb + g.slot_off[e] * plan.esz;
@@ -1421,11 +1411,79 @@ void halo_stencil_regions(HaloStencilArgs& a, const HaloNdPlan& plan,
       r.wd = (unsigned)g.ww[e];
     } else {
       r.kind = STENCIL_OFFSET;
-      r.shift = (g.sy[e] - g.ry[e]) * nx + (g.sx[e] - g.rx[e]);
+      r.shift = (g.sy[e] - g.ry[e]) * x.nx + (g.sx[e] - g.rx[e]);
     }
   }
 }
 
+// What the three argument structs have in common: the field pointers and,
+// for apply, the region table.
+template <typename Args>
+void halo_stencil_io(Args& a, const HaloNdPlan& plan,
+                     const std::vector<at::Tensor>& fields,
+                     const std::vector<at::Tensor>& outs, const HaloCall& x,
+                     bool transposed) {
+  for (int64_t k = 0; k < plan.nf; ++k) {
+    a.in[k] = fields[k].data_ptr();
+    a.out[k] = outs[k].data_ptr();
+  }
+  if (!transposed) halo_stencil_regions(a.reg, plan, x);
+}
+
+// Constant coefficients in the accumulate type and in-plane offsets into
+// the LDS tile, negated for the transposed mode.
+template <typename Args>
+void halo_stencil_taps(Args& a, bool f64, int64_t w,
+                       const std::vector<int64_t>& tap_dy,
+                       const std::vector<int64_t>& tap_dx,
+                       const std::vector<double>& tap_coef,
+                       bool transposed) {
+  const int64_t stride = kStencilTileX + 2 * w;
+  for (size_t t = 0; t < tap_dy.size(); ++t) {
+    if (f64) {
+      a.coef.f64[t] = tap_coef[t];
+    } else {
+      a.coef.f32[t] = (float)tap_coef[t];
+    }
+    const int64_t off = tap_dy[t] * stride + tap_dx[t];
+    a.tap_off[t] = (int)(transposed ? -off : off);
+  }
+}
+
+// Checks and kernel arguments of the constant-coefficient entries.  Raises
+// before anything is enqueued.
+HaloStencilArgs halo_stencil_args(const char* who, const HaloNdPlan& plan,
+                                  const std::vector<at::Tensor>& fields,
+                                  const std::vector<at::Tensor>& outs,
+                                  const HaloCall& x,
+                                  const std::vector<int64_t>& tap_dy,
+                                  const std::vector<int64_t>& tap_dx,
+                                  const std::vector<double>& tap_coef,
+                                  bool transposed, unsigned* blocks) {
+  halo_stencil_checks(who, plan, fields, outs, tap_dy, tap_dx,
+                      tap_coef.size());
+  const TileGrid tg =
+      tile_grid(who, x.ny, x.nx, transposed ? 0 : plan.w, kStencilTileY,
+                kStencilTileX, plan.nf * x.levels, "planes");
+  *blocks = tg.blocks;
+  HaloStencilArgs a{};
+  halo_stencil_io(a, plan, fields, outs, x, transposed);
+  halo_stencil_taps(a, fields[0].scalar_type() == at::kDouble, plan.w,
+                    tap_dy, tap_dx, tap_coef, transposed);
+  a.ny = x.ny;
+  a.nx = x.nx;
+  a.levels = (unsigned)x.levels;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
+  a.w = (int)plan.w;
+  a.ntaps = (int)tap_dy.size();
+  return a;
+}
+
+// Native executor of HaloStencil.apply: outs = P_int . S . E (fields),
+// the fields themselves never written.  Arguments as halo_exchange_nd,
+// plus the outputs and the taps (dy, dx, coefficient) in the order they
+// are added.
 void halo_stencil_nd(std::vector<at::Tensor> fields,
                      std::vector<at::Tensor> outs, int64_t levels,
                      int64_t ny, int64_t nx, int64_t width,
@@ -1437,25 +1495,17 @@ void halo_stencil_nd(std::vector<at::Tensor> fields,
                      at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil_nd");
   const char* who = "halo_stencil_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
-  HaloStencilArgs a =
-      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, false, &blocks);
-  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
-
+  const HaloStencilArgs a =
+      halo_stencil_args(who, plan, fields, outs, x, tap_dy, tap_dx, tap_coef,
+                        false, &blocks);
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    HIP_CHECK(launch_halo_stencil(a, 0, dt, blocks, cur_stream()));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloStencilNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_stencil(a, 0, dt, blocks, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(who, "HaloStencilNd", plan, x, [&](hipStream_t s) {
+    return launch_halo_stencil(a, 0, dt, blocks, s);
+  });
 }
 
 // ---- Krylov layer over the stencil (parallel/cg.StencilCG, krylov.hip)
@@ -1542,21 +1592,15 @@ KrylovArgs krylov_args(const char* who,
                   who, ": bad field ", k, " of list ", li);
     }
   }
-  const int64_t tiles_y = (ny - 2 * w + kStencilTileY - 1) / kStencilTileY;
-  const int64_t tiles_x = (nx - 2 * w + kStencilTileX - 1) / kStencilTileX;
-  const int64_t planes = nf * levels;
-  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
-  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
-                        planes * (tiles_y * tiles_x) < max_blocks,
-                    who, ": ", planes, " planes of ", tiles_y, " x ", tiles_x,
-                    " tiles exceed the launch limit of 2^24 blocks");
-  *blocks = (unsigned)(planes * tiles_y * tiles_x);
+  const TileGrid tg = tile_grid(who, ny, nx, w, kStencilTileY, kStencilTileX,
+                               nf * levels, "planes");
+  *blocks = tg.blocks;
   KrylovArgs a{};
   a.ny = ny;
   a.nx = nx;
   a.levels = (unsigned)levels;
-  a.tiles_y = (unsigned)tiles_y;
-  a.tiles_x = (unsigned)tiles_x;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
   a.w = (int)w;
   return a;
 }
@@ -1584,6 +1628,26 @@ void krylov_fields_disjoint(const char* who,
   }
 }
 
+struct DotBufs {
+  double* partials;
+  double* result;
+};
+
+// The checks the three *_dot_nd entries make of `partials` (one slot per
+// block) and `result`: neither lies inside an output or the other.
+DotBufs krylov_dot_bufs(const char* who, const at::Tensor& partials,
+                        const at::Tensor& result,
+                        const std::vector<at::Tensor>& outs,
+                        unsigned blocks) {
+  const at::Device dev = outs[0].device();
+  const DotBufs b{krylov_partials(who, partials, dev, blocks),
+                  krylov_scalar(who, "result", result, dev)};
+  krylov_no_overlap(who, partials, "partials", outs);
+  krylov_no_overlap(who, result, "result", outs);
+  krylov_no_overlap(who, result, "result", {partials});
+  return b;
+}
+
 // HaloStencil.apply_dot: halo_stencil_nd with the kernel's DOT epilogue,
 // then the finish launch: result = fields . outs over the interior of
 // this rank, in float64.  Same paths, same stored outputs.
@@ -1599,37 +1663,23 @@ void halo_stencil_dot_nd(std::vector<at::Tensor> fields,
                          at::Tensor partials, at::Tensor result) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil_dot_nd");
   const char* who = "halo_stencil_dot_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
   HaloStencilArgs a =
-      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, false, &blocks);
-  const at::Device dev = fields[0].device();
-  a.partials = krylov_partials(who, partials, dev, blocks);
-  double* res = krylov_scalar(who, "result", result, dev);
-  krylov_no_overlap(who, partials, "partials", outs);
-  krylov_no_overlap(who, result, "result", outs);
-  krylov_no_overlap(who, result, "result", {partials});
-  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
-  CommEntry c{};  // looked up only to be checked before the first launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
+      halo_stencil_args(who, plan, fields, outs, x, tap_dy, tap_dx, tap_coef,
+                        false, &blocks);
+  const DotBufs d = krylov_dot_bufs(who, partials, result, outs, blocks);
+  a.partials = d.partials;
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    hipStream_t stream = cur_stream();
-    HIP_CHECK(launch_halo_stencil_dot(a, dt, blocks, stream));
-    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloStencilDotNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_stencil_dot(a, dt, blocks, sent.stream));
-  HIP_CHECK(
-      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(who, "HaloStencilDotNd", plan, x, [&](hipStream_t s) {
+    const hipError_t e = launch_halo_stencil_dot(a, dt, blocks, s);
+    return e != hipSuccess
+               ? e
+               : launch_krylov_finish(d.partials, blocks, d.result, nullptr,
+                                      s);
+  });
 }
 
 // One Chebyshev iteration of parallel/chebyshev.StencilChebyshev on the
@@ -1652,17 +1702,17 @@ void halo_cheb_step_nd(std::vector<at::Tensor> d_in,
                        double c1, double c2) {
   ROCTX_SCOPE("mpi4jax_amd::halo_cheb_step_nd");
   const char* who = "halo_cheb_step_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, d_in, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall hc{levels, ny, nx, width, send_to, recv_from, local_mask,
+                    sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, d_in, hc);
   const auto st = d_in[0].scalar_type();
   TORCH_CHECK(st == at::kFloat || st == at::kDouble, who,
               " supports float32 and float64, got ", st);
   unsigned blocks = 0;
   HaloChebArgs a{};
   static_cast<HaloStencilArgs&>(a) =
-      halo_stencil_args(who, plan, d_in, d_out, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, false, &blocks);
+      halo_stencil_args(who, plan, d_in, d_out, hc, tap_dy, tap_dx, tap_coef,
+                        false, &blocks);
   const std::vector<at::Tensor>* lists[2] = {&x, &r};
   for (int li = 0; li < 2; ++li) {
     TORCH_CHECK((int64_t)lists[li]->size() == plan.nf, who, ": ", plan.nf,
@@ -1691,20 +1741,10 @@ void halo_cheb_step_nd(std::vector<at::Tensor> d_in,
   }
   a.c1 = c1;
   a.c2 = c2;
-  halo_stencil_regions(a, plan, recv_from, rbuf, nx);
-  CommEntry c{};  // looked up only to be checked before the first launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
   const int dt = dt_code(d_in[0]);
-  if (!plan.any_remote) {
-    HIP_CHECK(launch_halo_stencil_cheb(a, dt, blocks, cur_stream()));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloChebStepNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_stencil_cheb(a, dt, blocks, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(who, "HaloChebStepNd", plan, hc, [&](hipStream_t s) {
+    return launch_halo_stencil_cheb(a, dt, blocks, s);
+  });
 }
 
 // HaloStencil.dot: result = a . b over the interior of this rank.  a and
@@ -1827,22 +1867,17 @@ ZLineArgs zline_args(const char* who,
                     kZlineMaxLds / per_plane, "), got ", lds_planes);
   const int64_t nf = (int64_t)lists[0]->size();
   const int64_t columns = levels / nz;
-  const int64_t tiles_y = (ny - 2 * w + kZlineTileY - 1) / kZlineTileY;
-  const int64_t tiles_x = (nx - 2 * w + kZlineTileX - 1) / kZlineTileX;
-  const int64_t max_blocks = ((int64_t)1 << 32) / kZlineBlock;
-  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
-                        nf * columns * (tiles_y * tiles_x) < max_blocks,
-                    who, ": ", nf * columns, " columns of ", tiles_y, " x ",
-                    tiles_x, " tiles exceed the launch limit of 2^24 blocks");
-  *blocks = (unsigned)(nf * columns * tiles_y * tiles_x);
+  const TileGrid tg = tile_grid(who, ny, nx, w, kZlineTileY, kZlineTileX,
+                               nf * columns, "columns");
+  *blocks = tg.blocks;
   ZLineArgs a{};
   a.tables = tables.data_ptr();
   a.ny = ny;
   a.nx = nx;
   a.nz = (unsigned)nz;
   a.columns = (unsigned)columns;
-  a.tiles_y = (unsigned)tiles_y;
-  a.tiles_x = (unsigned)tiles_x;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
   a.lds_planes = (unsigned)lds_planes;
   a.w = (int)w;
   a.periodic = periodic ? 1 : 0;
@@ -1920,9 +1955,8 @@ void halo_zline_pcg_update_nd(
                                  (double*)a.num, old, stream));
 }
 
-// Native executor of HaloStencil.adjoint: gins = E^T . S^T . P_int (gouts).
-// One launch of the stencil kernel's transposed mode writes every cell of
-// `gins`; halo_adjoint_nd then runs in place on them.
+// Native executor of HaloStencil.adjoint: halo_stencil_adjoint_sequence
+// with the stencil kernel's transposed mode.
 void halo_stencil_adjoint_nd(std::vector<at::Tensor> gouts,
                              std::vector<at::Tensor> gins, int64_t levels,
                              int64_t ny, int64_t nx, int64_t width,
@@ -1935,51 +1969,36 @@ void halo_stencil_adjoint_nd(std::vector<at::Tensor> gouts,
                              at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil_adjoint_nd");
   const char* who = "halo_stencil_adjoint_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, x);
   unsigned blocks = 0;
   const HaloStencilArgs a =
-      halo_stencil_args(who, plan, gouts, gins, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, true, &blocks);
-  // everything halo_adjoint_nd will ask of `gins`, before the launch
-  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
-  CommEntry c{};  // looked up only to be checked before the launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
-  HIP_CHECK(launch_halo_stencil(a, 1, dt_code(gouts[0]), blocks,
-                                cur_stream()));
-  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
-                  std::move(recv_from), local_mask, std::move(sbuf),
-                  std::move(rbuf), comm_id);
+      halo_stencil_args(who, plan, gouts, gins, x, tap_dy, tap_dx, tap_coef,
+                        true, &blocks);
+  const int dt = dt_code(gouts[0]);
+  halo_stencil_adjoint_sequence(plan, gouts, gins, x, [&](hipStream_t s) {
+    return launch_halo_stencil(a, 1, dt, blocks, s);
+  });
 }
 
 // ---- variable-coefficient halo stencil
 // (parallel/varstencil.VariableHaloStencil, varstencil.hip)
 
-// Checks and kernel arguments of the three entries below.  Everything
-// halo_stencil_args asks of the fields, the outputs and the offsets is
-// asked here through it; `coef` is the (ntaps, ny, nx) tensor of
-// coefficients in the accumulate type and `lpb` the levels per block.
-// Raises before anything is enqueued.
+// Checks and kernel arguments of the three entries below; `coef` is the
+// (ntaps, ny, nx) tensor of coefficients in the accumulate type and `lpb`
+// the levels per block.  Raises before anything is enqueued.
 HaloVarStencilArgs halo_varstencil_args(
     const char* who, const HaloNdPlan& plan,
     const std::vector<at::Tensor>& fields, const std::vector<at::Tensor>& outs,
-    int64_t levels, int64_t ny, int64_t nx,
-    const std::vector<int64_t>& tap_dy, const std::vector<int64_t>& tap_dx,
-    const at::Tensor& coef, int64_t lpb,
-    const std::vector<int64_t>& recv_from, const at::Tensor& rbuf,
+    const HaloCall& x, const std::vector<int64_t>& tap_dy,
+    const std::vector<int64_t>& tap_dx, const at::Tensor& coef, int64_t lpb,
     bool transposed, unsigned* blocks) {
+  const int64_t levels = x.levels, ny = x.ny, nx = x.nx;
   const size_t nt = tap_dy.size();
   TORCH_CHECK(nt >= 1 && nt <= (size_t)kVarStencilMaxTaps, who,
               ": the number of taps must be in 1..", kVarStencilMaxTaps);
-  unsigned unused = 0;
-  HaloStencilArgs c =
-      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
-                        tap_dx, std::vector<double>(nt, 0.0), transposed,
-                        &unused);
-  if (!transposed) halo_stencil_regions(c, plan, recv_from, rbuf, nx);
-  const int64_t nf = plan.nf, w = plan.w;
+  halo_stencil_checks(who, plan, fields, outs, tap_dy, tap_dx, nt);
   const bool f64 = fields[0].scalar_type() == at::kDouble;
   TORCH_CHECK(coef.is_cuda() && coef.device() == fields[0].device() &&
                   coef.is_contiguous() && coef.dim() == 3 &&
@@ -1993,26 +2012,15 @@ HaloVarStencilArgs halo_varstencil_args(
   TORCH_CHECK_VALUE(lpb >= 1 && lpb <= levels, who,
                     ": levels per block must be in 1..", levels, ", got ",
                     lpb);
-  const int64_t ty =
-      4 * (f64 ? kVarStencilRowsF64 : kVarStencilRowsF32);
-  const int64_t org = transposed ? 0 : w;
-  const int64_t tiles_y = (ny - 2 * org + ty - 1) / ty;
-  const int64_t tiles_x = (nx - 2 * org + kStencilTileX - 1) / kStencilTileX;
   const int64_t chunks = (levels + lpb - 1) / lpb;
-  const int64_t max_blocks = ((int64_t)1 << 32) / kStencilBlock;
-  TORCH_CHECK_VALUE(tiles_y * tiles_x < max_blocks &&
-                        nf * chunks * (tiles_y * tiles_x) < max_blocks,
-                    who, ": ", nf * chunks, " level chunks of ", tiles_y,
-                    " x ", tiles_x,
-                    " tiles exceed the launch limit of 2^24 blocks");
-  *blocks = (unsigned)(nf * chunks * tiles_y * tiles_x);
+  const TileGrid tg = tile_grid(
+      who, ny, nx, transposed ? 0 : plan.w,
+      4 * (f64 ? kVarStencilRowsF64 : kVarStencilRowsF32), kStencilTileX,
+      plan.nf * chunks, "level chunks");
+  *blocks = tg.blocks;
 
   HaloVarStencilArgs a{};
-  for (int64_t k = 0; k < nf; ++k) {
-    a.in[k] = c.in[k];
-    a.out[k] = c.out[k];
-  }
-  for (int k = 0; k < 9; ++k) a.reg[k] = c.reg[k];
+  halo_stencil_io(a, plan, fields, outs, x, transposed);
   a.coef = coef.data_ptr();
   for (size_t t = 0; t < nt; ++t) {
     a.tap_dy[t] = (int)tap_dy[t];
@@ -2023,17 +2031,15 @@ HaloVarStencilArgs halo_varstencil_args(
   a.levels = (unsigned)levels;
   a.lpb = (unsigned)lpb;
   a.chunks = (unsigned)chunks;
-  a.tiles_y = (unsigned)tiles_y;
-  a.tiles_x = (unsigned)tiles_x;
-  a.w = (int)w;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
+  a.w = (int)plan.w;
   a.ntaps = (int)nt;
   return a;
 }
 
 // Native executor of VariableHaloStencil.apply: halo_stencil_nd with the
-// coefficient tensor in place of tap_coef, and the levels per block.  No
-// remote entry: ONE launch.  Otherwise the exchanger's pack launch, its
-// RCCL group and one launch reading the receive slots.
+// coefficient tensor in place of tap_coef, and the levels per block.
 void halo_varstencil_nd(std::vector<at::Tensor> fields,
                         std::vector<at::Tensor> outs, int64_t levels,
                         int64_t ny, int64_t nx, int64_t width,
@@ -2044,23 +2050,17 @@ void halo_varstencil_nd(std::vector<at::Tensor> fields,
                         at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_nd");
   const char* who = "halo_varstencil_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
-  const HaloVarStencilArgs a = halo_varstencil_args(
-      who, plan, fields, outs, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
-      recv_from, rbuf, false, &blocks);
+  const HaloVarStencilArgs a =
+      halo_varstencil_args(who, plan, fields, outs, x, tap_dy, tap_dx, coef,
+                           lpb, false, &blocks);
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    HIP_CHECK(launch_halo_varstencil(a, 0, dt, blocks, cur_stream()));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloVarStencilNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_varstencil(a, 0, dt, blocks, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(who, "HaloVarStencilNd", plan, x, [&](hipStream_t s) {
+    return launch_halo_varstencil(a, 0, dt, blocks, s);
+  });
 }
 
 // VariableHaloStencil.apply_dot: halo_varstencil_nd with the kernel's DOT
@@ -2077,41 +2077,28 @@ void halo_varstencil_dot_nd(std::vector<at::Tensor> fields,
                             at::Tensor partials, at::Tensor result) {
   ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_dot_nd");
   const char* who = "halo_varstencil_dot_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
-  HaloVarStencilArgs a = halo_varstencil_args(
-      who, plan, fields, outs, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
-      recv_from, rbuf, false, &blocks);
-  const at::Device dev = fields[0].device();
-  a.partials = krylov_partials(who, partials, dev, blocks);
-  double* res = krylov_scalar(who, "result", result, dev);
-  krylov_no_overlap(who, partials, "partials", outs);
-  krylov_no_overlap(who, result, "result", outs);
-  krylov_no_overlap(who, result, "result", {partials});
-  CommEntry c{};  // looked up only to be checked before the first launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
+  HaloVarStencilArgs a =
+      halo_varstencil_args(who, plan, fields, outs, x, tap_dy, tap_dx, coef,
+                           lpb, false, &blocks);
+  const DotBufs d = krylov_dot_bufs(who, partials, result, outs, blocks);
+  a.partials = d.partials;
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    hipStream_t stream = cur_stream();
-    HIP_CHECK(launch_halo_varstencil(a, 2, dt, blocks, stream));
-    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloVarStencilDotNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_varstencil(a, 2, dt, blocks, sent.stream));
-  HIP_CHECK(
-      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(
+      who, "HaloVarStencilDotNd", plan, x, [&](hipStream_t s) {
+        const hipError_t e = launch_halo_varstencil(a, 2, dt, blocks, s);
+        return e != hipSuccess
+                   ? e
+                   : launch_krylov_finish(d.partials, blocks, d.result,
+                                          nullptr, s);
+      });
 }
 
-// Native executor of VariableHaloStencil.adjoint: one launch of the
-// kernel's transposed mode writes every cell of `gins`; halo_adjoint_nd
-// then runs in place on them.
+// Native executor of VariableHaloStencil.adjoint:
+// halo_stencil_adjoint_sequence with this kernel's transposed mode.
 void halo_varstencil_adjoint_nd(std::vector<at::Tensor> gouts,
                                 std::vector<at::Tensor> gins, int64_t levels,
                                 int64_t ny, int64_t nx, int64_t width,
@@ -2123,50 +2110,44 @@ void halo_varstencil_adjoint_nd(std::vector<at::Tensor> gouts,
                                 at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_varstencil_adjoint_nd");
   const char* who = "halo_varstencil_adjoint_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, x);
   unsigned blocks = 0;
-  const HaloVarStencilArgs a = halo_varstencil_args(
-      who, plan, gouts, gins, levels, ny, nx, tap_dy, tap_dx, coef, lpb,
-      recv_from, rbuf, true, &blocks);
-  // everything halo_adjoint_nd will ask of `gins`, before the launch
-  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
-  CommEntry c{};  // looked up only to be checked before the launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
-  HIP_CHECK(launch_halo_varstencil(a, 1, dt_code(gouts[0]), blocks,
-                                   cur_stream()));
-  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
-                  std::move(recv_from), local_mask, std::move(sbuf),
-                  std::move(rbuf), comm_id);
+  const HaloVarStencilArgs a =
+      halo_varstencil_args(who, plan, gouts, gins, x, tap_dy, tap_dx, coef,
+                           lpb, true, &blocks);
+  const int dt = dt_code(gouts[0]);
+  halo_stencil_adjoint_sequence(plan, gouts, gins, x, [&](hipStream_t s) {
+    return launch_halo_varstencil(a, 1, dt, blocks, s);
+  });
 }
 
 // ---- 3-D halo stencil (parallel/stencil3d.HaloStencil3D, stencil3d.hip)
 
-// Checks and kernel arguments of the three entries below.  Everything
-// halo_stencil_args asks of the fields, the outputs and the in-plane
-// offsets is asked here through it.  `nz` is the z extent (levels =
-// columns * nz), `tap_dz` the taps' z offsets, sorted, `zc` the output
-// planes per block.  Raises before anything is enqueued.
+// Checks and kernel arguments of the three entries below.  `nz` is the z
+// extent (levels = columns * nz), `tap_dz` the taps' z offsets, sorted,
+// `zc` the output planes per block.  Raises before anything is enqueued.
 HaloStencil3dArgs halo_stencil3d_args(
     const char* who, const HaloNdPlan& plan,
     const std::vector<at::Tensor>& fields, const std::vector<at::Tensor>& outs,
-    int64_t levels, int64_t nz, int64_t ny, int64_t nx,
-    const std::vector<int64_t>& tap_dz, const std::vector<int64_t>& tap_dy,
-    const std::vector<int64_t>& tap_dx, const std::vector<double>& tap_coef,
-    int64_t zc, bool periodic_z, const std::vector<int64_t>& recv_from,
-    const at::Tensor& rbuf, bool transposed, unsigned* blocks) {
+    const HaloCall& x, int64_t nz, const std::vector<int64_t>& tap_dz,
+    const std::vector<int64_t>& tap_dy, const std::vector<int64_t>& tap_dx,
+    const std::vector<double>& tap_coef, int64_t zc, bool periodic_z,
+    bool transposed, unsigned* blocks) {
+  const int64_t levels = x.levels;
   const size_t nt = tap_dz.size();
   TORCH_CHECK(nt >= 1 && nt <= (size_t)kStencil3dMaxTaps &&
                   tap_dy.size() == nt,
               who, ": the four tap lists must have one length in 1..",
               kStencil3dMaxTaps);
-  unsigned unused = 0;
-  HaloStencilArgs c =
-      halo_stencil_args(who, plan, fields, outs, levels, ny, nx, tap_dy,
-                        tap_dx, tap_coef, transposed, &unused);
-  if (!transposed) halo_stencil_regions(c, plan, recv_from, rbuf, nx);
+  halo_stencil_checks(who, plan, fields, outs, tap_dy, tap_dx,
+                      tap_coef.size());
+  // chunks <= nz, so the kernel's grid has at most the nf * levels * tiles
+  // blocks that are checked here
+  const TileGrid tg =
+      tile_grid(who, x.ny, x.nx, transposed ? 0 : plan.w, kStencilTileY,
+                kStencilTileX, plan.nf * levels, "planes");
   int64_t rz = 0;
   for (size_t t = 0; t < nt; ++t) {
     rz = std::max(rz, std::max(tap_dz[t], -tap_dz[t]));
@@ -2181,45 +2162,30 @@ HaloStencil3dArgs halo_stencil3d_args(
                     ": periodic z needs nz >= ", 2 * rz + 1, ", got ", nz);
   TORCH_CHECK_VALUE(zc >= 1 && zc <= nz, who,
                     ": planes per block must be in 1..", nz, ", got ", zc);
-  const int64_t nf = plan.nf, w = plan.w;
   const int64_t columns = levels / nz;
   const int64_t chunks = (nz + zc - 1) / zc;
-  const int64_t tiles = (int64_t)c.tiles_y * c.tiles_x;
-  // chunks <= nz, so this grid has at most the nf * levels * tiles blocks
-  // that halo_stencil_args has checked against the launch limit of 2^24
-  *blocks = (unsigned)(nf * columns * chunks * tiles);
+  *blocks = (unsigned)(plan.nf * columns * chunks * tg.tiles_y * tg.tiles_x);
 
   HaloStencil3dArgs a{};
-  for (int64_t k = 0; k < nf; ++k) {
-    a.in[k] = c.in[k];
-    a.out[k] = c.out[k];
-  }
-  for (int k = 0; k < 9; ++k) a.reg[k] = c.reg[k];
-  const bool f64 = fields[0].scalar_type() == at::kDouble;
-  for (size_t t = 0; t < nt; ++t) {
-    if (f64) {
-      a.coef.f64[t] = c.coef.f64[t];
-    } else {
-      a.coef.f32[t] = c.coef.f32[t];
-    }
-    a.tap_off[t] = c.tap_off[t];
-  }
+  halo_stencil_io(a, plan, fields, outs, x, transposed);
+  halo_stencil_taps(a, fields[0].scalar_type() == at::kDouble, plan.w,
+                    tap_dy, tap_dx, tap_coef, transposed);
   // tap_begin[j]: the first tap with dz >= j - rz
   for (int64_t j = 0; j <= 2 * rz + 1; ++j) {
     size_t t = 0;
     while (t < nt && tap_dz[t] < j - rz) ++t;
     a.tap_begin[j] = (int)t;
   }
-  a.ny = ny;
-  a.nx = nx;
+  a.ny = x.ny;
+  a.nx = x.nx;
   a.levels = (unsigned)levels;
   a.nz = (unsigned)nz;
   a.columns = (unsigned)columns;
   a.zc = (unsigned)zc;
   a.chunks = (unsigned)chunks;
-  a.tiles_y = c.tiles_y;
-  a.tiles_x = c.tiles_x;
-  a.w = (int)w;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
+  a.w = (int)plan.w;
   a.rz = (int)rz;
   a.ntaps = (int)nt;
   a.periodic_z = periodic_z ? 1 : 0;
@@ -2227,9 +2193,7 @@ HaloStencil3dArgs halo_stencil3d_args(
 }
 
 // Native executor of HaloStencil3D.apply: halo_stencil_nd's launch
-// sequence with the 3-D kernel.  No remote entry: ONE launch.  Otherwise
-// the exchanger's pack launch, its RCCL group and one launch reading the
-// receive slots.
+// sequence with the 3-D kernel.
 void halo_stencil3d_nd(std::vector<at::Tensor> fields,
                        std::vector<at::Tensor> outs, int64_t levels,
                        int64_t nz, int64_t ny, int64_t nx, int64_t width,
@@ -2242,23 +2206,17 @@ void halo_stencil3d_nd(std::vector<at::Tensor> fields,
                        at::Tensor sbuf, at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_nd");
   const char* who = "halo_stencil3d_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
   const HaloStencil3dArgs a = halo_stencil3d_args(
-      who, plan, fields, outs, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
-      tap_coef, zc, periodic_z, recv_from, rbuf, false, &blocks);
+      who, plan, fields, outs, x, nz, tap_dz, tap_dy, tap_dx, tap_coef, zc,
+      periodic_z, false, &blocks);
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    HIP_CHECK(launch_halo_stencil3d(a, 0, dt, blocks, cur_stream()));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloStencil3dNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_stencil3d(a, 0, dt, blocks, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(who, "HaloStencil3dNd", plan, x, [&](hipStream_t s) {
+    return launch_halo_stencil3d(a, 0, dt, blocks, s);
+  });
 }
 
 // HaloStencil3D.apply_dot: halo_stencil3d_nd with the kernel's DOT
@@ -2277,41 +2235,28 @@ void halo_stencil3d_dot_nd(std::vector<at::Tensor> fields,
                            at::Tensor partials, at::Tensor result) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_dot_nd");
   const char* who = "halo_stencil3d_dot_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, fields, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, fields, x);
   unsigned blocks = 0;
   HaloStencil3dArgs a = halo_stencil3d_args(
-      who, plan, fields, outs, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
-      tap_coef, zc, periodic_z, recv_from, rbuf, false, &blocks);
-  const at::Device dev = fields[0].device();
-  a.partials = krylov_partials(who, partials, dev, blocks);
-  double* res = krylov_scalar(who, "result", result, dev);
-  krylov_no_overlap(who, partials, "partials", outs);
-  krylov_no_overlap(who, result, "result", outs);
-  krylov_no_overlap(who, result, "result", {partials});
-  CommEntry c{};  // looked up only to be checked before the first launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
+      who, plan, fields, outs, x, nz, tap_dz, tap_dy, tap_dx, tap_coef, zc,
+      periodic_z, false, &blocks);
+  const DotBufs d = krylov_dot_bufs(who, partials, result, outs, blocks);
+  a.partials = d.partials;
   const int dt = dt_code(fields[0]);
-  if (!plan.any_remote) {
-    hipStream_t stream = cur_stream();
-    HIP_CHECK(launch_halo_stencil3d(a, 2, dt, blocks, stream));
-    HIP_CHECK(launch_krylov_finish(a.partials, blocks, res, nullptr, stream));
-    return;
-  }
-  const HaloNdSent sent =
-      halo_exchange_send("HaloStencil3dDotNd", plan, levels, ny, nx, send_to,
-                         recv_from, local_mask, sbuf, rbuf, comm_id);
-  HIP_CHECK(launch_halo_stencil3d(a, 2, dt, blocks, sent.stream));
-  HIP_CHECK(
-      launch_krylov_finish(a.partials, blocks, res, nullptr, sent.stream));
-  watchdog_arm(who, sent.rank, sent.stream);
+  halo_stencil_sequence(
+      who, "HaloStencil3dDotNd", plan, x, [&](hipStream_t s) {
+        const hipError_t e = launch_halo_stencil3d(a, 2, dt, blocks, s);
+        return e != hipSuccess
+                   ? e
+                   : launch_krylov_finish(d.partials, blocks, d.result,
+                                          nullptr, s);
+      });
 }
 
-// Native executor of HaloStencil3D.adjoint: one launch of the kernel's
-// transposed mode writes every cell of `gins`; halo_adjoint_nd then runs
-// in place on them.
+// Native executor of HaloStencil3D.adjoint: halo_stencil_adjoint_sequence
+// with this kernel's transposed mode.
 void halo_stencil3d_adjoint_nd(std::vector<at::Tensor> gouts,
                                std::vector<at::Tensor> gins, int64_t levels,
                                int64_t nz, int64_t ny, int64_t nx,
@@ -2325,23 +2270,17 @@ void halo_stencil3d_adjoint_nd(std::vector<at::Tensor> gouts,
                                at::Tensor rbuf, int64_t comm_id) {
   ROCTX_SCOPE("mpi4jax_amd::halo_stencil3d_adjoint_nd");
   const char* who = "halo_stencil3d_adjoint_nd";
-  const HaloNdPlan plan = halo_nd_plan(who, gouts, levels, ny, nx, width,
-                                       send_to, recv_from, local_mask, sbuf,
-                                       rbuf);
+  const HaloCall x{levels, ny, nx, width, send_to, recv_from, local_mask,
+                   sbuf, rbuf, comm_id};
+  const HaloNdPlan plan = halo_nd_plan(who, gouts, x);
   unsigned blocks = 0;
   const HaloStencil3dArgs a = halo_stencil3d_args(
-      who, plan, gouts, gins, levels, nz, ny, nx, tap_dz, tap_dy, tap_dx,
-      tap_coef, zc, periodic_z, recv_from, rbuf, true, &blocks);
-  // everything halo_adjoint_nd will ask of `gins`, before the launch
-  halo_adjoint_checks(plan, gouts, levels, ny, nx, sbuf, rbuf);
-  CommEntry c{};  // looked up only to be checked before the launch
-  halo_peers(plan, comm_id, send_to, recv_from, &c);
-
-  HIP_CHECK(launch_halo_stencil3d(a, 1, dt_code(gouts[0]), blocks,
-                                  cur_stream()));
-  halo_adjoint_nd(std::move(gins), levels, ny, nx, width, std::move(send_to),
-                  std::move(recv_from), local_mask, std::move(sbuf),
-                  std::move(rbuf), comm_id);
+      who, plan, gouts, gins, x, nz, tap_dz, tap_dy, tap_dx, tap_coef, zc,
+      periodic_z, true, &blocks);
+  const int dt = dt_code(gouts[0]);
+  halo_stencil_adjoint_sequence(plan, gouts, gins, x, [&](hipStream_t s) {
+    return launch_halo_stencil3d(a, 1, dt, blocks, s);
+  });
 }
 
 // direct access to the combine kernel (used by gpu numerics tests)

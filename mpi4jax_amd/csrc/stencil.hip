@@ -44,6 +44,7 @@
 #include "halo_types.h"
 #include "kernels.h"
 #include "krylov_reduce.h"
+#include "stencil_cells.h"
 
 #include <cstdint>
 #include <type_traits>
@@ -65,33 +66,6 @@ static_assert(2 * kStencilMaxWidth <= kStTX,
               "the apron columns are filled by one partial pass");
 static_assert(kStBlock == kKrylovBlock,
               "the dot epilogue reduces over a block of the Krylov size");
-
-template <typename Acc>
-__device__ inline Acc stencil_coef(const HaloStencilArgs& a, int t);
-template <>
-__device__ inline float stencil_coef<float>(const HaloStencilArgs& a, int t) {
-  return a.coef.f32[t];
-}
-template <>
-__device__ inline double stencil_coef<double>(const HaloStencilArgs& a,
-                                              int t) {
-  return a.coef.f64[t];
-}
-
-// The value the exchange would have put into halo cell (y, x) of plane
-// `pl` (= field * levels + level), read from where it comes from.
-template <typename T, typename Acc>
-__device__ inline Acc stencil_halo_cell(const HaloStencilArgs& a,
-                                        const T* plane, unsigned pl,
-                                        long long y, long long x, int k) {
-  const StencilRegion& r = a.reg[k];
-  if (r.kind == STENCIL_SLOT) {
-    const long long s =
-        ((long long)pl * r.h + (y - r.ry)) * r.wd + (x - r.rx);
-    return adj_load<T, Acc>((const T*)r.buf + s);
-  }
-  return adj_load<T, Acc>(plane + (y * a.nx + x + r.shift));  // OWN: shift 0
-}
 
 template <typename T, typename Acc, int MODE, bool DOT = false,
           bool CHEB = false>
@@ -150,24 +124,8 @@ __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
     for (int r = wrow; r < rows; r += kStWaves) {
       const long long y = fy0 + r;
       for (int c = lane; c < S; c += kStTX) {
-        const long long x = fx0 + c;
-        Acc v = Acc(0);
-        if (MODE == 0) {
-          // y, x >= 0 here; cells past the plane feed no stored output
-          if (y < ny && x < nx) {
-            const int ky = y < w ? 0 : (y >= ny - w ? 2 : 1);
-            const int kx = x < w ? 0 : (x >= nx - w ? 2 : 1);
-            v = (ky == 1 && kx == 1)
-                    ? adj_load<T, Acc>(in + (y * nx + x))
-                    : stencil_halo_cell<T, Acc>(a, in, pl, y, x,
-                                                ky * 3 + kx);
-          }
-        } else {
-          if (y >= w && y < ny - w && x >= w && x < nx - w) {
-            v = adj_load<T, Acc>(in + (y * nx + x));
-          }
-        }
-        tile[r * S + c] = v;
+        tile[r * S + c] =
+            stencil_slow_cell<T, Acc, MODE>(a, in, pl, y, fx0 + c, w, ny, nx);
       }
     }
   }
@@ -253,11 +211,16 @@ __global__ __launch_bounds__(kStBlock) void halo_stencil_kernel(
   }
 }
 
+// Bytes of the LDS tile at halo width w.
+template <typename Acc>
+size_t stencil_lds_bytes(int w) {
+  return (size_t)(kStTY + 2 * w) * (kStTX + 2 * w) * sizeof(Acc);
+}
+
 template <typename T, typename Acc>
 void launch_stencil_t(const HaloStencilArgs& a, int mode, unsigned blocks,
                       hipStream_t stream) {
-  const size_t lds = (size_t)(kStTY + 2 * a.w) * (kStTX + 2 * a.w) *
-                     sizeof(Acc);
+  const size_t lds = stencil_lds_bytes<Acc>(a.w);
   dim3 grid(blocks), block(kStBlock);
   if (mode == 0) {
     hipLaunchKernelGGL((halo_stencil_kernel<T, Acc, 0>), grid, block, lds,
@@ -271,19 +234,16 @@ void launch_stencil_t(const HaloStencilArgs& a, int mode, unsigned blocks,
 template <typename T, typename Acc>
 void launch_stencil_dot_t(const HaloStencilArgs& a, unsigned blocks,
                           hipStream_t stream) {
-  const size_t lds = (size_t)(kStTY + 2 * a.w) * (kStTX + 2 * a.w) *
-                     sizeof(Acc);
   hipLaunchKernelGGL((halo_stencil_kernel<T, Acc, 0, true>), dim3(blocks),
-                     dim3(kStBlock), lds, stream, a);
+                     dim3(kStBlock), stencil_lds_bytes<Acc>(a.w), stream, a);
 }
 
 template <typename T>
 void launch_stencil_cheb_t(const HaloChebArgs& a, unsigned blocks,
                            hipStream_t stream) {
-  const size_t lds = (size_t)(kStTY + 2 * a.w) * (kStTX + 2 * a.w) *
-                     sizeof(T);
   hipLaunchKernelGGL((halo_stencil_kernel<T, T, 0, false, true>),
-                     dim3(blocks), dim3(kStBlock), lds, stream, a);
+                     dim3(blocks), dim3(kStBlock), stencil_lds_bytes<T>(a.w),
+                     stream, a);
 }
 
 }  // namespace

@@ -44,6 +44,7 @@
 #include "halo_types.h"
 #include "kernels.h"
 #include "krylov_reduce.h"
+#include "stencil_cells.h"
 
 #include <cstdint>
 
@@ -61,34 +62,6 @@ static_assert(kS3Block == kKrylovBlock,
               "the dot epilogue reduces over a block of the Krylov size");
 static_assert(2 * kStencilMaxWidth <= kS3TX,
               "the apron columns are filled by one partial pass");
-
-template <typename Acc>
-__device__ inline Acc stencil3d_coef(const HaloStencil3dArgs& a, int t);
-template <>
-__device__ inline float stencil3d_coef<float>(const HaloStencil3dArgs& a,
-                                              int t) {
-  return a.coef.f32[t];
-}
-template <>
-__device__ inline double stencil3d_coef<double>(const HaloStencil3dArgs& a,
-                                                int t) {
-  return a.coef.f64[t];
-}
-
-// The value the exchange would have put into halo cell (y, x) of plane
-// `pl` (= field * levels + level), read from where it comes from.
-template <typename T, typename Acc>
-__device__ inline Acc stencil3d_halo_cell(const HaloStencil3dArgs& a,
-                                          const T* plane, unsigned pl,
-                                          long long y, long long x, int k) {
-  const StencilRegion& r = a.reg[k];
-  if (r.kind == STENCIL_SLOT) {
-    const long long s =
-        ((long long)pl * r.h + (y - r.ry)) * r.wd + (x - r.rx);
-    return adj_load<T, Acc>((const T*)r.buf + s);
-  }
-  return adj_load<T, Acc>(plane + (y * a.nx + x + r.shift));  // OWN: shift 0
-}
 
 // One input plane `in` (plane index `pl` of the slot layout) into the LDS
 // buffer `tile`: rows fy0 .. of (kS3TY + 2w) x (kS3TX + 2w) cells.
@@ -128,24 +101,8 @@ __device__ inline void stencil3d_fill(const HaloStencil3dArgs& a, Acc* tile,
   for (int r = wrow; r < rows; r += kS3Waves) {
     const long long y = fy0 + r;
     for (int c = lane; c < S; c += kS3TX) {
-      const long long x = fx0 + c;
-      Acc v = Acc(0);
-      if (MODE == 0) {
-        // y, x >= 0 here; cells past the plane feed no stored output
-        if (y < ny && x < nx) {
-          const int ky = y < w ? 0 : (y >= ny - w ? 2 : 1);
-          const int kx = x < w ? 0 : (x >= nx - w ? 2 : 1);
-          v = (ky == 1 && kx == 1)
-                  ? adj_load<T, Acc>(in + (y * nx + x))
-                  : stencil3d_halo_cell<T, Acc>(a, in, pl, y, x,
-                                                ky * 3 + kx);
-        }
-      } else {
-        if (y >= w && y < ny - w && x >= w && x < nx - w) {
-          v = adj_load<T, Acc>(in + (y * nx + x));
-        }
-      }
-      tile[r * S + c] = v;
+      tile[r * S + c] =
+          stencil_slow_cell<T, Acc, MODE>(a, in, pl, y, fx0 + c, w, ny, nx);
     }
   }
 }
@@ -233,7 +190,7 @@ __global__ __launch_bounds__(kS3Block) void halo_stencil3d_kernel(
         const int k = s - DIR * (j - RZ);  // the output plane of dz = j - RZ
         if (k < z0 || k >= z1) continue;   // another chunk's, or none
         for (int t = a.tap_begin[j]; t < a.tap_begin[j + 1]; ++t) {
-          const Acc c = stencil3d_coef<Acc>(a, t);
+          const Acc c = stencil_coef<Acc>(a, t);
           const Acc* p = cur + (base + a.tap_off[t]);
 #pragma unroll
           for (int r = 0; r < kS3Rows; ++r) {

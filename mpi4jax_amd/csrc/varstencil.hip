@@ -40,6 +40,7 @@
 #include "halo_types.h"
 #include "kernels.h"
 #include "krylov_reduce.h"
+#include "stencil_cells.h"
 
 #include <cstdint>
 
@@ -54,21 +55,6 @@ static_assert(kVsBlock == kKrylovBlock,
               "the dot epilogue reduces over a block of the Krylov size");
 static_assert(2 * kStencilMaxWidth <= kVsTX,
               "the apron columns are filled by one partial pass");
-
-// The value the exchange would have put into halo cell (y, x) of plane
-// `pl` (= field * levels + level), read from where it comes from.
-template <typename T, typename Acc>
-__device__ inline Acc varstencil_halo_cell(const HaloVarStencilArgs& a,
-                                           const T* plane, unsigned pl,
-                                           long long y, long long x, int k) {
-  const StencilRegion& r = a.reg[k];
-  if (r.kind == STENCIL_SLOT) {
-    const long long s =
-        ((long long)pl * r.h + (y - r.ry)) * r.wd + (x - r.rx);
-    return adj_load<T, Acc>((const T*)r.buf + s);
-  }
-  return adj_load<T, Acc>(plane + (y * a.nx + x + r.shift));  // OWN: shift 0
-}
 
 template <typename T, typename Acc, int ROWS, int MODE, bool DOT>
 __global__ __launch_bounds__(kVsBlock) void halo_varstencil_kernel(
@@ -169,24 +155,8 @@ __global__ __launch_bounds__(kVsBlock) void halo_varstencil_kernel(
       for (int r = wrow; r < rows; r += kVsWaves) {
         const long long y = fy0 + r;
         for (int c = lane; c < S; c += kVsTX) {
-          const long long cx = fx0 + c;
-          Acc v = Acc(0);
-          if (MODE == 0) {
-            // y, cx >= 0 here; cells past the plane feed no stored output
-            if (y < ny && cx < nx) {
-              const int ky = y < w ? 0 : (y >= ny - w ? 2 : 1);
-              const int kx = cx < w ? 0 : (cx >= nx - w ? 2 : 1);
-              v = (ky == 1 && kx == 1)
-                      ? adj_load<T, Acc>(in + (y * nx + cx))
-                      : varstencil_halo_cell<T, Acc>(a, in, pl, y, cx,
-                                                     ky * 3 + kx);
-            }
-          } else {
-            if (y >= w && y < ny - w && cx >= w && cx < nx - w) {
-              v = adj_load<T, Acc>(in + (y * nx + cx));
-            }
-          }
-          tile[r * S + c] = v;
+          tile[r * S + c] =
+              stencil_slow_cell<T, Acc, MODE>(a, in, pl, y, fx0 + c, w, ny, nx);
         }
       }
     }

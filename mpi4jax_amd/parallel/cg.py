@@ -128,7 +128,7 @@ class StencilCG:
                         f"x[{k}] overlaps "
                         + (f"x[{j}]" if j < len(x) else f"b[{j - len(x)}]"))
         if st._native():  # q = A x
-            st._call_native("halo_stencil_nd", x, self._q)
+            st._apply_native(x, self._q)
         else:
             st._apply_py(x, self._q)
         for fb, fr, fp, fq in zip(b, self._r, self._p, self._q):

@@ -163,7 +163,7 @@ class StencilChebyshev:
         self._cur = 0
         d, q = self._d[0], self._d[1]  # the other d buffer holds A x
         if st._native():
-            st._call_native("halo_stencil_nd", x, q)
+            st._apply_native(x, q)
         else:
             st._apply_py(x, q)
         for fb, fr, fd, fq in zip(b, self._r, d, q):

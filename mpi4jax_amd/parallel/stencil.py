@@ -60,6 +60,9 @@ from .halo import AD_DTYPES, HaloExchanger
 
 MAX_RADIUS = 4
 TILE_Y, TILE_X = 32, 64  # kStencilTileY, kStencilTileX of csrc/kernels.h
+# Blocks per compute unit that _pick_chunk keeps: measured for the
+# variable-coefficient kernel, carried over to the 3-D one unmeasured.
+_BLOCKS_PER_CU = 4
 
 
 def _parse_weights(weights):
@@ -88,6 +91,16 @@ def _parse_weights(weights):
     return r, taps
 
 
+def _pick_chunk(extent, blocks_per_chunk, compute_units):
+    """How much of ``extent`` (levels, or planes of a column) one block of
+    a marching kernel takes when a chunk of the extent costs
+    ``blocks_per_chunk`` blocks: the whole extent when that still leaves
+    ``_BLOCKS_PER_CU`` blocks per compute unit, else the largest chunk that
+    does, else 1."""
+    chunks = -(-_BLOCKS_PER_CU * compute_units // blocks_per_chunk)  # wanted
+    return max(1, extent // chunks) if chunks <= extent else 1
+
+
 def _span(t):
     lo = t.data_ptr()
     return lo, lo + t.numel() * t.element_size()
@@ -97,24 +110,33 @@ class HaloStencil:
     """See the module docstring.  Build with
     ``CartesianGrid.make_stencil``."""
 
+    # the family's entries of csrc/bridge.cpp: each takes _native_args, then
+    # the exchange arguments; the dot entry also the partials and the result
+    _APPLY = "halo_stencil_nd"
+    _APPLY_DOT = "halo_stencil_dot_nd"
+    _ADJOINT = "halo_stencil_adjoint_nd"
+
     def __init__(self, grid, shape, dtype, device, weights, nfields=1,
                  _force_remote=False):
+        self._init_dtype(dtype)
+        self._width, self._taps = _parse_weights(weights)
+        self.exchanger = HaloExchanger(
+            grid, shape, dtype, device, width=self._width, nfields=nfields,
+            _force_remote=_force_remote)
+        self._tap_dy = [t[0] for t in self._taps]
+        self._tap_dx = [t[1] for t in self._taps]
+        self._tap_coef = [t[2] for t in self._taps]
+
+    def _init_dtype(self, dtype):
         if not isinstance(dtype, torch.dtype):
             raise TypeError(f"dtype must be a torch.dtype, got {dtype!r}")
         if dtype not in AD_DTYPES:
             raise TypeError(
                 f"a halo stencil supports float16, bfloat16, float32 and "
                 f"float64, got {dtype}")
-        self._width, self._taps = _parse_weights(weights)
-        self.exchanger = HaloExchanger(
-            grid, shape, dtype, device, width=self._width, nfields=nfields,
-            _force_remote=_force_remote)
         self.dtype = dtype
         self.acc_dtype = (torch.float64 if dtype == torch.float64
                           else torch.float32)
-        self._tap_dy = [t[0] for t in self._taps]
-        self._tap_dx = [t[1] for t in self._taps]
-        self._tap_coef = [t[2] for t in self._taps]
         self._partials = None  # see _partials_buf
 
     @property
@@ -165,7 +187,7 @@ class HaloStencil:
         ex._check(fields)
         outs = self._outputs(fields, out, zero=True)
         if self._native():
-            self._call_native("halo_stencil_nd", fields, outs)
+            self._apply_native(fields, outs)
         else:
             self._apply_py(fields, outs)
         return self._ret(outs)
@@ -192,7 +214,7 @@ class HaloStencil:
                 raise ValueError(
                     f"halo adjoint over {ex._adj_work} frame cells "
                     f"exceeds the native executor's 2^31 limit")
-            self._call_native("halo_stencil_adjoint_nd", gouts, gins)
+            self._adjoint_native(gouts, gins)
         else:
             self._adjoint_py(gouts, gins)
         return self._ret(gins)
@@ -212,12 +234,9 @@ class HaloStencil:
         (32 x 64 tiles of the interior of every plane), allocated once."""
         if self._partials is None:
             ex = self.exchanger
-            w = self._width
-            tiles = (-(-(ex.ny - 2 * w) // TILE_Y)
-                     * -(-(ex.nx - 2 * w) // TILE_X))
             self._partials = torch.empty(
-                ex.nfields * ex.levels * tiles, dtype=torch.float64,
-                device=ex.device)
+                ex.nfields * ex.levels * self._tiles(TILE_Y),
+                dtype=torch.float64, device=ex.device)
         return self._partials
 
     def _allreduce_(self, scalar):
@@ -272,15 +291,8 @@ class HaloStencil:
 
     def _apply_dot_into(self, fields, outs, result):
         if self._native():
-            from .._backend import rccl
-
-            ex = self.exchanger
-            comm_id = rccl._handle(ex.comm) if ex._has_remote else -1
-            rccl.ext().halo_stencil_dot_nd(
-                list(fields), list(outs), ex.levels, ex.ny, ex.nx,
-                self._width, self._tap_dy, self._tap_dx, self._tap_coef,
-                ex._send_to, ex._recv_from, ex._local_mask, ex._sbuf,
-                ex._rbuf, comm_id, self._partials_buf(), result)
+            self._run_native(self._APPLY_DOT, fields, outs,
+                             self._partials_buf(), result)
             return self._allreduce_(result)
         self._apply_py(fields, outs)
         return self._dot_into(fields, outs, result)
@@ -330,15 +342,51 @@ class HaloStencil:
         return StencilChebyshev(self, lmin, lmax)
 
     # ------------------------------------------------------------------
-    def _call_native(self, entry, ins, outs):
+    def _tiles(self, tile_y):
+        """Tiles of ``tile_y`` x ``TILE_X`` cells over a plane's interior."""
+        ex = self.exchanger
+        w = self._width
+        return (-(-(ex.ny - 2 * w) // tile_y)
+                * -(-(ex.nx - 2 * w) // TILE_X))
+
+    def _chunk(self, forced, name, extent, blocks_per_chunk):
+        """The chunk of ``extent`` one block marches over: ``forced`` (the
+        constructor keyword ``name``) when given, 1 off the GPU, else
+        ``_pick_chunk`` for this device."""
+        ex = self.exchanger
+        if forced is not None:
+            if (isinstance(forced, bool) or not isinstance(forced, int)
+                    or not 1 <= forced <= extent):
+                raise ValueError(
+                    f"{name} must be an int in 1..{extent}, got {forced!r}")
+            return forced
+        if ex.device.type != "cuda":
+            return 1
+        cus = torch.cuda.get_device_properties(
+            ex.device).multi_processor_count
+        return _pick_chunk(extent, blocks_per_chunk, cus)
+
+    def _native_args(self, ins, outs):
+        """What the family's native entries take before the exchange
+        arguments."""
+        ex = self.exchanger
+        return (list(ins), list(outs), ex.levels, ex.ny, ex.nx, self._width,
+                self._tap_dy, self._tap_dx, self._tap_coef)
+
+    def _run_native(self, entry, ins, outs, *more):
         from .._backend import rccl
 
         ex = self.exchanger
         comm_id = rccl._handle(ex.comm) if ex._has_remote else -1
         getattr(rccl.ext(), entry)(
-            list(ins), list(outs), ex.levels, ex.ny, ex.nx, self._width,
-            self._tap_dy, self._tap_dx, self._tap_coef, ex._send_to,
-            ex._recv_from, ex._local_mask, ex._sbuf, ex._rbuf, comm_id)
+            *self._native_args(ins, outs), ex._send_to, ex._recv_from,
+            ex._local_mask, ex._sbuf, ex._rbuf, comm_id, *more)
+
+    def _apply_native(self, ins, outs):
+        self._run_native(self._APPLY, ins, outs)
+
+    def _adjoint_native(self, gouts, gins):
+        self._run_native(self._ADJOINT, gouts, gins)
 
     def _apply_py(self, fields, outs):
         ex = self.exchanger

@@ -20,8 +20,8 @@ With ``E`` and ``P_int`` exactly as in :mod:`.stencil`:
   ``K_t * gout[b, k - dz_t, p - (dy_t, dx_t)]`` over the taps whose source
   cell is interior and whose source plane exists; ``ex.adjoint_`` then runs
   in place;
-* ``apply_ad``, ``dot``, ``apply_dot`` and ``make_cg()`` are those of
-  :class:`~.stencil.HaloStencil`;
+* ``apply_ad``, ``dot``, ``apply_dot`` and ``make_cg()`` are inherited
+  from :class:`~.stencil.HaloStencil`;
 * ``make_line_solver`` solves with the tridiagonal part of ``A`` along z
   (:mod:`.zline`), and ``make_cg("zline")`` uses that as the
   preconditioner of conjugate gradients (:mod:`.pcg`).
@@ -33,7 +33,11 @@ modulo ``nz``, which needs ``nz >= 2 rz + 1``.
 
 Executors: the native one (default on the GPU) is ``csrc/stencil3d.hip``
 through ``bridge.cpp:halo_stencil3d_nd`` / ``_dot_nd`` / ``_adjoint_nd``
-with the launch sequences of the 2-D stencil.  A block owns one 32 x 64
+with the launch sequences of the 2-D stencil.  The class only names these
+three entries and lists the arguments they take before the exchange's
+(``_native_args``); :class:`~.stencil.HaloStencil` makes the calls, so the
+solvers of :mod:`.cg` and :mod:`.pcg` drive every stencil through the same
+methods.  A block owns one 32 x 64
 tile of one column and marches over ``z_chunk`` output planes with one
 input plane resident in LDS and ``2 rz + 1`` output planes in registers.
 The Python executor (the CPU path, or ``MPI4JAX_AMD_HALO_PY=1``) runs
@@ -44,17 +48,11 @@ viewed as ``(B, nz, ny, nx)``.  There is no 3-D Chebyshev kernel:
 
 import torch
 
-from .halo import AD_DTYPES, HaloExchanger
-from .stencil import MAX_RADIUS, TILE_X, TILE_Y, HaloStencil
+from .halo import HaloExchanger
+from .stencil import MAX_RADIUS, TILE_Y, HaloStencil
 
 MAX_TAPS = 32  # kStencil3dMaxTaps of csrc/kernels.h
 MAX_RZ = 2     # kStencil3dMaxRz
-# Blocks per compute unit that _pick_z_chunk keeps: carried over from
-# varstencil.py, not measured for this kernel.
-_BLOCKS_PER_CU = 4
-
-_NATIVE = {"halo_stencil_nd": "halo_stencil3d_nd",
-           "halo_stencil_adjoint_nd": "halo_stencil3d_adjoint_nd"}
 
 
 def _parse_weights3d(weights):
@@ -90,14 +88,13 @@ class HaloStencil3D(HaloStencil):
     """See the module docstring.  Build with
     ``CartesianGrid.make_stencil3d``."""
 
+    _APPLY = "halo_stencil3d_nd"
+    _APPLY_DOT = "halo_stencil3d_dot_nd"
+    _ADJOINT = "halo_stencil3d_adjoint_nd"
+
     def __init__(self, grid, shape, dtype, device, weights, nfields=1,
                  z_boundary="zero", _force_remote=False, _z_chunk=None):
-        if not isinstance(dtype, torch.dtype):
-            raise TypeError(f"dtype must be a torch.dtype, got {dtype!r}")
-        if dtype not in AD_DTYPES:
-            raise TypeError(
-                f"a halo stencil supports float16, bfloat16, float32 and "
-                f"float64, got {dtype}")
+        self._init_dtype(dtype)
         if z_boundary not in ("zero", "periodic"):
             raise ValueError(
                 f"z_boundary must be 'zero' or 'periodic', got "
@@ -113,18 +110,16 @@ class HaloStencil3D(HaloStencil):
             raise ValueError(
                 f"periodic z needs nz >= 2*rz+1 = {2 * self._rz + 1}, got "
                 f"nz = {nz}")
-        self.exchanger = HaloExchanger(
+        self.exchanger = ex = HaloExchanger(
             grid, shape, dtype, device, width=self._width, nfields=nfields,
             _force_remote=_force_remote)
-        self.dtype = dtype
-        self.acc_dtype = (torch.float64 if dtype == torch.float64
-                          else torch.float32)
         self._tap_dz = [t[0] for t in self._taps]
         self._tap_dy = [t[1] for t in self._taps]
         self._tap_dx = [t[2] for t in self._taps]
         self._tap_coef = [t[3] for t in self._taps]
-        self._partials = None
-        self._zc = self._pick_z_chunk(_z_chunk)
+        self._zc = self._chunk(
+            _z_chunk, "_z_chunk", nz,
+            ex.nfields * (ex.levels // nz) * self._tiles(TILE_Y))
 
     @property
     def z_radius(self):
@@ -186,55 +181,11 @@ class HaloStencil3D(HaloStencil):
         return StencilPCG(self, _lds_planes=_lds_planes)
 
     # ------------------------------------------------------------------
-    def _pick_z_chunk(self, forced):
-        """The whole ``nz`` when that still leaves ``_BLOCKS_PER_CU``
-        blocks per compute unit, else the largest chunk that does, else
-        1."""
-        ex = self.exchanger
-        nz = self.nz
-        if forced is not None:
-            if (isinstance(forced, bool) or not isinstance(forced, int)
-                    or not 1 <= forced <= nz):
-                raise ValueError(
-                    f"_z_chunk must be an int in 1..{nz}, got {forced!r}")
-            return forced
-        if ex.device.type != "cuda":
-            return 1
-        cus = torch.cuda.get_device_properties(
-            ex.device).multi_processor_count
-        w = self._width
-        tiles = (-(-(ex.ny - 2 * w) // TILE_Y)
-                 * -(-(ex.nx - 2 * w) // TILE_X))
-        per_chunk = ex.nfields * (ex.levels // nz) * tiles
-        chunks = -(-_BLOCKS_PER_CU * cus // per_chunk)  # chunks wanted
-        return max(1, nz // chunks) if chunks <= nz else 1
-
     def _native_args(self, ins, outs):
-        from .._backend import rccl
-
         ex = self.exchanger
-        comm_id = rccl._handle(ex.comm) if ex._has_remote else -1
         return (list(ins), list(outs), ex.levels, self.nz, ex.ny, ex.nx,
                 self._width, self._tap_dz, self._tap_dy, self._tap_dx,
-                self._tap_coef, self._zc, self.z_boundary == "periodic",
-                ex._send_to, ex._recv_from, ex._local_mask, ex._sbuf,
-                ex._rbuf, comm_id)
-
-    def _call_native(self, entry, ins, outs):
-        from .._backend import rccl
-
-        getattr(rccl.ext(), _NATIVE[entry])(*self._native_args(ins, outs))
-
-    def _apply_dot_into(self, fields, outs, result):
-        if self._native():
-            from .._backend import rccl
-
-            rccl.ext().halo_stencil3d_dot_nd(
-                *self._native_args(fields, outs), self._partials_buf(),
-                result)
-            return self._allreduce_(result)
-        self._apply_py(fields, outs)
-        return self._dot_into(fields, outs, result)
+                self._tap_coef, self._zc, self.z_boundary == "periodic")
 
     def _z_terms(self, dz):
         """``(periodic, lo, hi)``: the planes ``k`` in ``[lo, hi)`` have a

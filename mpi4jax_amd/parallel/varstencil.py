@@ -17,7 +17,7 @@ With ``E`` and ``P_int`` exactly as in :mod:`.stencil`:
   ``p`` of the full array with the sum, in the same order and from 0, of
   ``K_t[p - o_t] * gout[p - o_t]`` over the taps whose source cell
   ``p - o_t`` is interior;
-* ``apply_dot``, ``dot``, ``apply_ad`` and ``make_cg`` are those of
+* ``apply_dot``, ``dot``, ``apply_ad`` and ``make_cg`` are inherited from
   :class:`~.stencil.HaloStencil`.  CG needs a symmetric operator, which is
   the caller's business: ``K_t[c] == K_{-t}[c + o_t]`` for every cell
   ``c``, across rank edges too.
@@ -32,7 +32,11 @@ overwrites it in place.
 
 Executors: the native one (default on the GPU) is ``csrc/varstencil.hip``
 through ``bridge.cpp:halo_varstencil_nd`` / ``_dot_nd`` / ``_adjoint_nd``,
-with the launch sequences of the constant stencil; a block keeps the
+with the launch sequences of the constant stencil.  The class only names
+these three entries and lists the arguments they take before the
+exchange's (``_native_args``); :class:`~.stencil.HaloStencil` makes the
+calls, so the solvers of :mod:`.cg` drive every stencil through the same
+methods.  A block keeps the
 coefficients of its tile in registers while it marches over
 ``levels_per_block`` consecutive levels, so coefficient traffic does not
 grow with the number of levels.  The Python executor (the CPU path, or
@@ -43,16 +47,12 @@ are constant-coefficient only and raise ``TypeError``.
 
 import torch
 
-from .stencil import MAX_RADIUS, TILE_X, TILE_Y, HaloStencil
-from .halo import AD_DTYPES, HaloExchanger
+from .stencil import MAX_RADIUS, TILE_Y, HaloStencil
+from .halo import HaloExchanger
 
 MAX_TAPS = 13  # kVarStencilMaxTaps of csrc/kernels.h
 # rows of a tile by accumulate type: 4 * kVarStencilRowsF32 / F64
 _TILE_Y = {torch.float32: 32, torch.float64: 16}
-_BLOCKS_PER_CU = 4  # see _pick_levels_per_block
-
-_NATIVE = {"halo_stencil_nd": "halo_varstencil_nd",
-           "halo_stencil_adjoint_nd": "halo_varstencil_adjoint_nd"}
 
 
 def _parse_offsets(offsets):
@@ -80,18 +80,14 @@ class VariableHaloStencil(HaloStencil):
     """See the module docstring.  Build with
     ``CartesianGrid.make_variable_stencil``."""
 
+    _APPLY = "halo_varstencil_nd"
+    _APPLY_DOT = "halo_varstencil_dot_nd"
+    _ADJOINT = "halo_varstencil_adjoint_nd"
+
     def __init__(self, grid, shape, dtype, device, offsets, coefficients,
                  nfields=1, _force_remote=False, _levels_per_block=None):
-        if not isinstance(dtype, torch.dtype):
-            raise TypeError(f"dtype must be a torch.dtype, got {dtype!r}")
-        if dtype not in AD_DTYPES:
-            raise TypeError(
-                f"a halo stencil supports float16, bfloat16, float32 and "
-                f"float64, got {dtype}")
+        self._init_dtype(dtype)
         self._width, self._offsets = _parse_offsets(offsets)
-        self.dtype = dtype
-        self.acc_dtype = (torch.float64 if dtype == torch.float64
-                          else torch.float32)
         self._tap_dy = [o[0] for o in self._offsets]
         self._tap_dx = [o[1] for o in self._offsets]
         shape = tuple(shape)
@@ -103,8 +99,9 @@ class VariableHaloStencil(HaloStencil):
         self._coef = torch.empty(self._coef_shape, dtype=self.acc_dtype,
                                  device=ex.device)
         self._coef.copy_(coefficients.detach())
-        self._partials = None
-        self._lpb = self._pick_levels_per_block(_levels_per_block)
+        self._lpb = self._chunk(
+            _levels_per_block, "_levels_per_block", ex.levels,
+            ex.nfields * self._tiles(_TILE_Y[self.acc_dtype]))
 
     def _check_coefficients(self, c):
         if not isinstance(c, torch.Tensor):
@@ -154,32 +151,6 @@ class VariableHaloStencil(HaloStencil):
                         "variable stencil has no Chebyshev kernel yet")
 
     # ------------------------------------------------------------------
-    def _tiles(self, tile_y):
-        ex = self.exchanger
-        w = self._width
-        return (-(-(ex.ny - 2 * w) // tile_y)
-                * -(-(ex.nx - 2 * w) // TILE_X))
-
-    def _pick_levels_per_block(self, forced):
-        """The whole level range when that still leaves
-        ``_BLOCKS_PER_CU`` blocks per compute unit, else the largest chunk
-        that does, else 1."""
-        ex = self.exchanger
-        if forced is not None:
-            if (isinstance(forced, bool) or not isinstance(forced, int)
-                    or not 1 <= forced <= ex.levels):
-                raise ValueError(
-                    f"_levels_per_block must be an int in 1..{ex.levels}, "
-                    f"got {forced!r}")
-            return forced
-        if ex.device.type != "cuda":
-            return 1
-        cus = torch.cuda.get_device_properties(
-            ex.device).multi_processor_count
-        per_chunk = ex.nfields * self._tiles(_TILE_Y[self.acc_dtype])
-        chunks = -(-_BLOCKS_PER_CU * cus // per_chunk)  # chunks wanted
-        return max(1, ex.levels // chunks) if chunks <= ex.levels else 1
-
     def _partials_buf(self):
         """One float64 slot per block of the largest native grid: the
         Krylov kernels' 32 x 64 tiles of every plane, or this kernel's
@@ -194,30 +165,9 @@ class VariableHaloStencil(HaloStencil):
         return self._partials
 
     def _native_args(self, ins, outs):
-        from .._backend import rccl
-
         ex = self.exchanger
-        comm_id = rccl._handle(ex.comm) if ex._has_remote else -1
         return (list(ins), list(outs), ex.levels, ex.ny, ex.nx, self._width,
-                self._tap_dy, self._tap_dx, self._coef, self._lpb,
-                ex._send_to, ex._recv_from, ex._local_mask, ex._sbuf,
-                ex._rbuf, comm_id)
-
-    def _call_native(self, entry, ins, outs):
-        from .._backend import rccl
-
-        getattr(rccl.ext(), _NATIVE[entry])(*self._native_args(ins, outs))
-
-    def _apply_dot_into(self, fields, outs, result):
-        if self._native():
-            from .._backend import rccl
-
-            rccl.ext().halo_varstencil_dot_nd(
-                *self._native_args(fields, outs), self._partials_buf(),
-                result)
-            return self._allreduce_(result)
-        self._apply_py(fields, outs)
-        return self._dot_into(fields, outs, result)
+                self._tap_dy, self._tap_dx, self._coef, self._lpb)
 
     def _apply_py(self, fields, outs):
         ex = self.exchanger

@@ -84,7 +84,8 @@ def build_native(force=False, variant=""):
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
         deps = [sp, CSRC / "kernels.h", CSRC / "halo_geom.h",
-                CSRC / "halo_types.h", CSRC / "krylov_reduce.h"]
+                CSRC / "halo_types.h", CSRC / "krylov_reduce.h",
+                CSRC / "stencil_cells.h"]
         variant_flags = []
         if variant == "nofma" and src.endswith(".hip"):
             variant_flags = ["-ffp-contract=off"]

@@ -282,6 +282,43 @@ def test_native_equals_python_executor_on_integer_data(grids, monkeypatch):
             assert torch.equal(a, b), (periodic, dtype)
 
 
+def check_executors_agree(st, x, monkeypatch):
+    """apply, apply_dot and adjoint of ``st`` on the integer-valued fields
+    ``x``: the native and the Python executor agree bitwise, and a second
+    native adjoint, which reuses the staging buffers, repeats the first."""
+    def run():
+        out, pap = st.apply_dot(*x)
+        return (as_tuple(st.apply(*x)) + as_tuple(out) + (pap,)
+                + as_tuple(st.adjoint(*x)))
+
+    monkeypatch.delenv("MPI4JAX_AMD_HALO_PY", raising=False)
+    native = run()
+    again = as_tuple(st.adjoint(*x))
+    monkeypatch.setenv("MPI4JAX_AMD_HALO_PY", "1")
+    py = run()
+    monkeypatch.delenv("MPI4JAX_AMD_HALO_PY", raising=False)
+    assert len(native) == len(py) == 3 * len(x) + 1
+    for i, (a, b) in enumerate(zip(native, py)):
+        assert torch.equal(a, b), i
+    for a, b in zip(native[-len(x):], again):
+        assert torch.equal(a, b), "the second adjoint differs"
+
+
+@pytest.mark.parametrize("force_remote", [False, True])
+@pytest.mark.parametrize("shape,w", [((2, 35, 67), 1), ((2, 41, 73), 4)])
+def test_executors_agree_on_ragged_tiles(grids, shape, w, force_remote,
+                                         monkeypatch):
+    """A ragged tile edge in both directions, two fields, both launch
+    sequences: every native entry of the family against the Python
+    executor."""
+    for dtype in (torch.float32, torch.float64):  # every value is exact
+        st = grids[(True, True)].make_stencil(
+            shape, dtype, "cuda", make_weights("full", w), nfields=2,
+            _force_remote=force_remote)
+        x = [int_data(shape, dtype, i, "cuda") for i in range(2)]
+        check_executors_agree(st, x, monkeypatch)
+
+
 # ---------------------------------------------------------------- autodiff
 
 def test_gradient_equals_cpu_on_integer_data(grids):

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 import mpi4jax_amd as m
 from mpi4jax_amd.parallel.grid import CartesianGrid
 from test_gpu_halo_exchanger import OPEN
+from test_gpu_halo_stencil import check_executors_agree
 from test_halo_adjoint import int_data
 from test_halo_stencil import as_tuple, check_bound, interior
 from test_stencil_cg import int_dot
@@ -107,6 +108,43 @@ def test_staged_exact(grids, name, zb, periodic):
     for shape, nf in itertools.product(shapes_for(k, zb)[:3], (1, 3)):
         run_exact(grids[periodic], k, zb, shape, nf,
                   (torch.float32, torch.bfloat16), _force_remote=True)
+
+
+@pytest.mark.parametrize("force_remote", [False, True])
+@pytest.mark.parametrize("zb", ZB)
+def test_executors_agree_on_ragged_tiles(grids, zb, force_remote,
+                                         monkeypatch):
+    """A ragged tile edge in both directions and a ragged last chunk of
+    planes (nz = 3 in chunks of 2), two columns, both launch sequences:
+    every native entry of the family against the Python executor."""
+    shape = (2, 3, 35, 67)
+    for dtype in (torch.float32, torch.float64):  # every value is exact
+        st = grids[(True, True)].make_stencil3d(
+            shape, dtype, "cuda", TAPSETS["box27"], nfields=2,
+            z_boundary=zb, _z_chunk=2, _force_remote=force_remote)
+        x = [int_data(shape, dtype, i, "cuda") for i in range(2)]
+        check_executors_agree(st, x, monkeypatch)
+
+
+def test_adjoint_checks_the_communicator_before_its_launch(grids):
+    """halo_stencil3d_adjoint_nd with a remote entry and a communicator
+    that does not exist raises and leaves the sentinel-filled outputs
+    alone: the lookup comes before the transposed launch."""
+    from mpi4jax_amd._backend import rccl
+
+    shape = (2, 3, 35, 67)
+    st = grids[(True, True)].make_stencil3d(
+        shape, torch.float32, "cuda", TAPSETS["star7"], _z_chunk=2,
+        _force_remote=True)
+    g = int_data(shape, torch.float32, 3, "cuda")
+    out = torch.full(shape, 7.0, device="cuda")
+    ex = st.exchanger
+    with pytest.raises(RuntimeError, match="unknown RCCL communicator"):
+        rccl.ext().halo_stencil3d_adjoint_nd(
+            *st._native_args([g], [out]), ex._send_to, ex._recv_from,
+            ex._local_mask, ex._sbuf, ex._rbuf, 123456)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
 
 
 @pytest.mark.parametrize("zb", ZB)

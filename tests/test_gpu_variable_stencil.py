@@ -13,6 +13,7 @@ import torch
 import mpi4jax_amd as m
 from mpi4jax_amd.parallel.grid import CartesianGrid
 from test_gpu_halo_exchanger import OPEN
+from test_gpu_halo_stencil import check_executors_agree
 from test_halo_adjoint import int_data
 from test_halo_stencil import as_tuple, check_bound, interior
 from test_stencil_cg import int_dot
@@ -100,6 +101,41 @@ def test_staged_path_exact(grids, periodic, name):
     for shape in shapes_for(radius(offsets))[:2]:
         run_exact(grids[periodic], offsets, shape, 3, (1, 2),
                   (torch.float32, torch.bfloat16), _force_remote=True)
+
+
+@pytest.mark.parametrize("force_remote", [False, True])
+def test_executors_agree_on_ragged_tiles(grids, force_remote, monkeypatch):
+    """A ragged tile edge in both directions and a ragged last chunk of
+    levels, both launch sequences: every native entry of the family against
+    the Python executor."""
+    offsets, shape = TAPSETS["box9"], (3, 35, 67)
+    for dtype in (torch.float32, torch.float64):  # every value is exact
+        st = grids[(True, True)].make_variable_stencil(
+            shape, dtype, "cuda", offsets, int_coef(offsets, shape, 2),
+            nfields=2, _levels_per_block=2, _force_remote=force_remote)
+        x = [int_data(shape, dtype, i, "cuda") for i in range(2)]
+        check_executors_agree(st, x, monkeypatch)
+
+
+def test_adjoint_checks_the_communicator_before_its_launch(grids):
+    """halo_varstencil_adjoint_nd with a remote entry and a communicator
+    that does not exist raises and leaves the sentinel-filled outputs
+    alone: the lookup comes before the transposed launch."""
+    from mpi4jax_amd._backend import rccl
+
+    offsets, shape = TAPSETS["star5"], (3, 35, 67)
+    st = grids[(True, True)].make_variable_stencil(
+        shape, torch.float32, "cuda", offsets, int_coef(offsets, shape, 1),
+        _levels_per_block=2, _force_remote=True)
+    g = int_data(shape, torch.float32, 3, "cuda")
+    out = torch.full(shape, 7.0, device="cuda")
+    ex = st.exchanger
+    with pytest.raises(RuntimeError, match="unknown RCCL communicator"):
+        rccl.ext().halo_varstencil_adjoint_nd(
+            *st._native_args([g], [out]), ex._send_to, ex._recv_from,
+            ex._local_mask, ex._sbuf, ex._rbuf, 123456)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

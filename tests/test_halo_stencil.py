@@ -448,6 +448,32 @@ def test_gradient_through_three_steps_equals_autograd(grids):
         assert ((got - ref).abs() <= bound).all(), periodic
 
 
+@pytest.mark.parametrize("cus,per_chunk,extent,want", [
+    (256, 2000, 64, 64),  # one chunk already gives 4 blocks per unit
+    (256, 1, 4096, 4),    # 1024 chunks wanted
+    (256, 1, 8, 1),       # more chunks wanted than there are planes
+    (256, 300, 10, 2),    # 4 chunks wanted: 10 // 4
+])
+def test_chunk_picker(grids, cus, per_chunk, extent, want):
+    """``_pick_chunk`` by hand: chunks wanted = ceil(4 * units / blocks per
+    chunk); the whole extent if that is 1, else ``extent // chunks``, else
+    1.  The marching stencils' ``_chunk`` returns a forced value as it is,
+    and 1 on the CPU."""
+    from mpi4jax_amd.parallel.stencil import _pick_chunk
+
+    assert _pick_chunk(extent, per_chunk, cus) == want
+    grid = grids[(True, True)]
+    var = grid.make_variable_stencil((5, 9, 10), torch.float32, "cpu",
+                                     [(0, 0), (0, 1)], torch.ones(2, 9, 10))
+    s3d = grid.make_stencil3d((5, 9, 10), torch.float32, "cpu",
+                              torch.ones(1, 3, 3))
+    for st, name in ((var, "_levels_per_block"), (s3d, "_z_chunk")):
+        assert st._chunk(None, name, extent, per_chunk) == 1
+        assert st._chunk(min(3, extent), name, extent, per_chunk) == \
+            min(3, extent)
+    assert var.levels_per_block == 1 and s3d.z_chunk == 1
+
+
 def test_errors(grids):
     grid = grids[(True, True)]
     ok = make_weights("star", 1)
