@@ -892,28 +892,21 @@ struct Upd2 {
   vf2 dnh, dnu, dnv, hh, uu, vv;
 };
 
-// fast-region update math for one 2-column pack (the stage19 body);
-// caller guarantees stage19_pair_fast(a, j, i0)
-template <bool NT>
-__device__ inline Upd2 stage19_math(const SwArgs<float>& a, int j,
-                                    int i0) {
-  const int nx = (int)a.nx;
-  const long long idx = (long long)j * nx + i0;
-  const long long idn = idx - nx, idp = idx + nx;
-
-  // all loads first (one vmcnt window), float4 per row
-  vf4 HmA = ld4(a.h, idn);      // h[j-1][0..3]
-  vf4 H0A = ld4(a.h, idx - 1);  // h[j][-1..2]
-  vf4 HpA = ld4(a.h, idp - 1);  // h[j+1][-1..2]
-  vf2 Um0 = ld2(a.u, idn);      // u[j-1][0..1]
-  vf4 U0A = ld4(a.u, idx - 1);  // u[j][-1..2]
-  vf4 UpA = ld4(a.u, idp - 1);  // u[j+1][-1..2]
-  vf4 VmA = ld4(a.v, idn);      // v[j-1][0..3]
-  vf4 V0A = ld4(a.v, idx - 1);  // v[j][-1..2]
-  vf2 Vp0 = ld2(a.v, idp);      // v[j+1][0..1]
-  vf2 doh = ld2s<NT>(a.doh, idx), dou = ld2s<NT>(a.dou, idx),
-      dov = ld2s<NT>(a.dov, idx);
-
+// fast-region update math for the 2-column pack at (j, i0) from its nine
+// row vectors (column offsets relative to i0; lane 3 of HmA/VmA/UpA is
+// not read) and its old tendencies — the single definition of the
+// stage-19 formulas, whatever memory the rows came from
+__device__ inline Upd2 stage19_update(const SwArgs<float>& a, int j,
+                                      vf4 HmA,   // h[j-1][0..3]
+                                      vf4 H0A,   // h[j][-1..2]
+                                      vf4 HpA,   // h[j+1][-1..2]
+                                      vf2 Um0,   // u[j-1][0..1]
+                                      vf4 U0A,   // u[j][-1..2]
+                                      vf4 UpA,   // u[j+1][-1..2]
+                                      vf4 VmA,   // v[j-1][0..3]
+                                      vf4 V0A,   // v[j][-1..2]
+                                      vf2 Vp0,   // v[j+1][0..1]
+                                      vf2 doh, vf2 dou, vf2 dov) {
   vf2 Hm0 = x01(HmA), Hm1 = x12(HmA);
   vf2 H0m1 = x01(H0A), H00 = x12(H0A), H01 = x23(H0A);
   vf2 Hpm1 = x01(HpA), Hp0 = x12(HpA), Hp1 = x23(HpA);
@@ -967,6 +960,31 @@ __device__ inline Upd2 stage19_math(const SwArgs<float>& a, int j,
   r.uu = U00 + a.dt * (a.ab_a * dnu + a.ab_b * dou);
   r.vv = V00 + a.dt * (a.ab_a * dnv + a.ab_b * dov);
   return r;
+}
+
+// the stage19 body with its rows loaded from global memory; caller
+// guarantees stage19_pair_fast(a, j, i0)
+template <bool NT>
+__device__ inline Upd2 stage19_math(const SwArgs<float>& a, int j,
+                                    int i0) {
+  const int nx = (int)a.nx;
+  const long long idx = (long long)j * nx + i0;
+  const long long idn = idx - nx, idp = idx + nx;
+
+  // all loads first (one vmcnt window), float4 per row
+  vf4 HmA = ld4(a.h, idn);
+  vf4 H0A = ld4(a.h, idx - 1);
+  vf4 HpA = ld4(a.h, idp - 1);
+  vf2 Um0 = ld2(a.u, idn);
+  vf4 U0A = ld4(a.u, idx - 1);
+  vf4 UpA = ld4(a.u, idp - 1);
+  vf4 VmA = ld4(a.v, idn);
+  vf4 V0A = ld4(a.v, idx - 1);
+  vf2 Vp0 = ld2(a.v, idp);
+  vf2 doh = ld2s<NT>(a.doh, idx), dou = ld2s<NT>(a.dou, idx),
+      dov = ld2s<NT>(a.dov, idx);
+  return stage19_update(a, j, HmA, H0A, HpA, Um0, U0A, UpA, VmA, V0A, Vp0,
+                        doh, dou, dov);
 }
 
 template <bool NT>
@@ -1466,6 +1484,159 @@ __device__ inline float s1_ab_update(float x, float dt, float aa, float dn,
   const float s = p + q;
   return __builtin_fmaf(dt, s, x);
 }
+// The same update as the compiler contracts it in the global-load fill
+// (stage19_update inlined into the vector pass): one product rounded, the
+// other fused into it, one FMA into x.  There the rounded product is
+// ab_a * dn for u and v and ab_b * dold for h; the staged fill spells
+// both out, so its results do not depend on what surrounds the call.
+__device__ inline vf2 s1_ab_update_fused(vf2 x, float dt, float c1, vf2 y1,
+                                         float c2, vf2 y2) {
+#pragma clang fp contract(off)
+  const vf2 p = c1 * y1;
+  return (vf2){__builtin_fmaf(dt, __builtin_fmaf(c2, y2.x, p.x), x.x),
+               __builtin_fmaf(dt, __builtin_fmaf(c2, y2.y, p.y), x.y)};
+}
+
+// Fast tiles stage their input through LDS.  The 16 x 32 fill pairs of
+// tile (jb, cb) read rows jb-2 .. jb+15 and columns cb-3 .. cb+62 of h, u
+// and v: an 18 x 66 window per field.  Loading every pair's 3-row stencil
+// from global memory (stage19_math) requests each element about six
+// times; here the block loads the window once, coalesced, and every fill
+// task reads its rows from LDS.  Window column 0 is field column cb-3, so
+// the (i0-1 .. i0+2) reads of pair lp start at the even column 2*lp: two
+// aligned 8-byte LDS reads per row.
+constexpr int kWR30 = kTR30 + 2;         // window rows
+constexpr int kWC30 = 2 * kTP30 + 2;     // window columns (and row pitch)
+constexpr int kWQ30 = (kWC30 - 2) / 4;   // 4-wide loads per window row
+constexpr int kWLd4 = kWR30 * kWQ30;     // 4-wide load positions
+constexpr int kWLoads = kWLd4 + kWR30;   // + one 2-wide position per row
+
+typedef float S1Win[3][kWR30][kWC30];  // h, u, v
+typedef float lf2 __attribute__((ext_vector_type(2)));  // 8-byte aligned
+
+// pass 1 of a fast tile: the stage-19 update of all 16 x 32 fill pairs
+// from the staged window, into the u'/v' tile and the owned outputs
+template <int NT_>
+__device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
+                                    int tid, S1Win& win, S30Tile& su,
+                                    S30Tile& sv) {
+  static_assert(kFill30 % NT_ == 0, "whole fill rounds");
+  constexpr int kRounds = (kWLoads + NT_ - 1) / NT_;
+  constexpr int kTasks = kFill30 / NT_;
+  const int nx = (int)a.nx;
+
+  // Window loads, all issued before anything waits on them; a thread
+  // loads one window position of all three fields.  None leaves the
+  // field's allocation: a fast tile has every fill pair stage19-fast, so
+  // rows jb-1 .. jb+14 lie in [jmin, jmax] within [1, ny-2] and the
+  // window rows jb-2 .. jb+15 in [0, ny-1]; the first fill pair has
+  // cb-2 >= imin >= 1, so cb-3 >= 0; the last one (i0 = cb+60) has
+  // i0 + 3 < nx, so cb+63 <= nx-1.  The 4-wide loads of a row cover
+  // columns cb-3 .. cb+60 (the last starts at cb+57 <= nx-7, never in the
+  // row's last 3 columns) and the 2-wide load covers cb+61, cb+62: every
+  // load stays inside its own row, the array's last row included.
+  const long long org = (long long)(jb - 2) * nx + (cb - 3);
+  vf4 wh[kRounds], wu[kRounds], wv[kRounds];
+#pragma unroll
+  for (int k = 0; k < kRounds; ++k) {
+    const int t = tid + k * NT_;
+    if ((k + 1) * NT_ <= kWLd4 || t < kWLd4) {
+      const long long o = org + (t / kWQ30 * nx + t % kWQ30 * 4);
+      wh[k] = ld4(a.h, o);
+      wu[k] = ld4(a.u, o);
+      wv[k] = ld4(a.v, o);
+    } else if (t < kWLoads) {
+      const long long o = org + ((t - kWLd4) * nx + 4 * kWQ30);
+      const vf2 xh = ld2(a.h, o), xu = ld2(a.u, o), xv = ld2(a.v, o);
+      wh[k] = (vf4){xh.x, xh.y, 0.f, 0.f};
+      wu[k] = (vf4){xu.x, xu.y, 0.f, 0.f};
+      wv[k] = (vf4){xv.x, xv.y, 0.f, 0.f};
+    }
+  }
+  // the old tendencies stay in global memory; an apron pair's h update
+  // is discarded, so it skips doh
+  vf2 doh[kTasks], dou[kTasks], dov[kTasks];
+#pragma unroll
+  for (int k = 0; k < kTasks; ++k) {
+    const int t = tid + k * NT_;
+    const int lr = t / kTP30, lp = t % kTP30;
+    const long long idx = (long long)(jb - 1 + lr) * nx + (cb - 2 + 2 * lp);
+    const bool owned = lr >= 1 && lr <= kTJ30 && lp >= 1 && lp <= kPC30;
+    dou[k] = ld2(a.dou, idx);
+    dov[k] = ld2(a.dov, idx);
+    doh[k] = owned ? ld2(a.doh, idx) : (vf2){0.f, 0.f};
+  }
+#pragma unroll
+  for (int k = 0; k < kRounds; ++k) {
+    const int t = tid + k * NT_;
+    if ((k + 1) * NT_ <= kWLd4 || t < kWLd4) {
+      const int r = t / kWQ30, c = t % kWQ30 * 4;
+      *(lf2*)&win[0][r][c] = (lf2){wh[k].x, wh[k].y};
+      *(lf2*)&win[0][r][c + 2] = (lf2){wh[k].z, wh[k].w};
+      *(lf2*)&win[1][r][c] = (lf2){wu[k].x, wu[k].y};
+      *(lf2*)&win[1][r][c + 2] = (lf2){wu[k].z, wu[k].w};
+      *(lf2*)&win[2][r][c] = (lf2){wv[k].x, wv[k].y};
+      *(lf2*)&win[2][r][c + 2] = (lf2){wv[k].z, wv[k].w};
+    } else if (t < kWLoads) {
+      const int r = t - kWLd4, c = 4 * kWQ30;
+      *(lf2*)&win[0][r][c] = (lf2){wh[k].x, wh[k].y};
+      *(lf2*)&win[1][r][c] = (lf2){wu[k].x, wu[k].y};
+      *(lf2*)&win[2][r][c] = (lf2){wv[k].x, wv[k].y};
+    }
+  }
+  __syncthreads();
+
+  // columns i0-1 .. i0+2 of window row wr, i0 the first column of pair lp
+  auto row4 = [&](int f, int wr, int lp) -> vf4 {
+    const lf2 p = *(const lf2*)&win[f][wr][2 * lp];
+    const lf2 q = *(const lf2*)&win[f][wr][2 * lp + 2];
+    return (vf4){p.x, p.y, q.x, q.y};
+  };
+  // the same row in stage19_update's [0..3] form (lane 3 is not read)
+  auto row4p = [&](int f, int wr, int lp) -> vf4 {
+    const vf4 A = row4(f, wr, lp);
+    return (vf4){A.y, A.z, A.w, A.w};
+  };
+  // A rolled loop: every fill task runs the one compiled body.  Unrolled,
+  // the compiler contracts the second task's expressions to FMA
+  // differently from the first's, and the 256-thread kernel (two tasks
+  // per thread) no longer equals the 512-thread one (one task) bitwise.
+  static_assert(kTasks <= 2, "the loop carries one task's tendencies");
+  vf2 toh = doh[0], tou = dou[0], tov = dov[0];
+#pragma unroll 1
+  for (int k = 0; k < kTasks; ++k) {
+    const int t = tid + k * NT_;
+    const int lr = t / kTP30, lp = t % kTP30;
+    const int rr = jb - 1 + lr;  // window row lr is field row rr - 1
+    const vf4 H0A = row4(0, lr + 1, lp), U0A = row4(1, lr + 1, lp),
+              V0A = row4(2, lr + 1, lp);
+    Upd2 r = stage19_update(
+        a, rr, row4p(0, lr, lp), H0A, row4(0, lr + 2, lp),
+        x01(row4p(1, lr, lp)), U0A, row4(1, lr + 2, lp), row4p(2, lr, lp),
+        V0A, x01(row4p(2, lr + 2, lp)), toh, tou, tov);
+    // the AB time update with its rounding spelled out (see
+    // s1_ab_update_fused): left to the compiler, the 256- and 512-thread
+    // instantiations contract it differently from each other and from
+    // the global-load fill
+    r.hh = s1_ab_update_fused(x12(H0A), a.dt, a.ab_b, toh, a.ab_a, r.dnh);
+    r.uu = s1_ab_update_fused(x12(U0A), a.dt, a.ab_a, r.dnu, a.ab_b, tou);
+    r.vv = s1_ab_update_fused(x12(V0A), a.dt, a.ab_a, r.dnv, a.ab_b, tov);
+    su[lr][2 * lp] = r.uu.x;
+    su[lr][2 * lp + 1] = r.uu.y;
+    sv[lr][2 * lp] = r.vv.x;
+    sv[lr][2 * lp + 1] = r.vv.y;
+    if (lr >= 1 && lr <= kTJ30 && lp >= 1 && lp <= kPC30) {
+      const long long idx = (long long)rr * nx + (cb - 2 + 2 * lp);
+      st2(a.dnh, idx, r.dnh);
+      st2(a.dnu, idx, r.dnu);
+      st2(a.dnv, idx, r.dnv);
+      st2(a.h2, idx, r.hh);
+    }
+    toh = doh[kTasks - 1];
+    tou = dou[kTasks - 1];
+    tov = dov[kTasks - 1];
+  }
+}
 
 template <int NT_>
 __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
@@ -1481,11 +1652,16 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
   const int tid = (int)threadIdx.x;
 
   __shared__ S30Tile su, sv;
+  __shared__ __attribute__((aligned(16))) S1Win win;
 
-  // pass 1, vector: the stage-19 update of every fast pair of the tile
-  // (sw_stage30t's fill loop minus the fe/fn strip stores; sharing one
-  // function changed both kernels' integer code, so the copy stays)
-  for (int t = tid; t < kFill30; t += NT_) {
+  // pass 1 of a fast tile: every fill pair from the staged window
+  if (!perim) s1_fast_fill<NT_>(a, jb, cb, tid, win, su, sv);
+
+  // pass 1 of a perimeter tile, vector: the stage-19 update of its fast
+  // pairs, rows from global memory (sw_stage30t's fill loop minus the
+  // fe/fn strip stores; sharing one function changed both kernels'
+  // integer code, so the copy stays)
+  for (int t = tid; perim && t < kFill30; t += NT_) {
     const int lr = t / kTP30, lp = t % kTP30;
     const int rr = jb - 1 + lr;
     const int i0 = cb - 2 + 2 * lp;
