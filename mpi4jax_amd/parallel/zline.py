@@ -17,8 +17,11 @@ not positive and finite raises ``ValueError``.  Periodic z factors the
 Sherman-Morrison matrix ``T'`` (``gamma = -b``, ``b_0' = b - gamma``,
 ``b_{nz-1}' = b - a c / gamma``) and adds ``qs = q / (1 + q_0 + g q_{nz-1})``
 with ``q = T'^{-1} (gamma, 0, .., 0, c)`` and ``g = a / gamma``.  With
-``a = c = 0`` both boundaries degenerate to a scaling by ``1 / b``.  The
-executors only multiply:
+``a = c = 0`` both boundaries degenerate to a scaling by ``1 / b``.  A
+periodic ``T`` is refused as singular when that denominator does not rise
+above the rounding noise of its own three terms, ``1024 nz eps64 (1 + |q_0|
++ |g q_{nz-1}|)``: for ``b = -(a + c)`` it is 0 in real arithmetic, and in
+float64 anything from 0 to ``eps64``.  The executors only multiply:
 
 * forward, ``k`` up: ``y_0 = r_0 inv_0``, ``y_k = (r_k - a y_{k-1}) inv_k``;
 * back, ``k`` down: ``s_{nz-1} = y_{nz-1}``, ``s_k = y_k - cp_k s_{k+1}``;
@@ -41,6 +44,7 @@ float32 and float64 only.
 """
 
 import math
+import sys
 
 import torch
 
@@ -49,10 +53,23 @@ from .cg import CG_DTYPES
 BLOCK = 256            # kZlineBlock of csrc/kernels.h
 TILE_Y, TILE_X = 4, 64  # kZlineTileY, kZlineTileX
 MAX_LDS = 65536 - 64   # kZlineMaxLds: 64 KiB less the reduction's slots
+# A periodic T counts as singular when its Sherman-Morrison denominator is
+# within this many nz * eps64 of the terms it sums (see _thomas).  Over nz in
+# 3..70 the singular bands (-1, 2, -1) give at most 0.09 of these units and
+# the nearly singular (-1, 2 + 1e-6, -1) 5e8.
+_SINGULAR = 1024.0
 
 
 def _thomas(nz, a, b, c, periodic):
-    """The four table rows as float64 lists: inv, cp, qs, lo."""
+    """The four table rows as float64 lists: inv, cp, qs, lo.
+
+    Raises ``ValueError`` for a pivot that is not positive and finite, and
+    under periodic z for a Sherman-Morrison denominator ``den = 1 + q_0 +
+    g q_{nz-1}`` that is not finite or not above ``_SINGULAR * nz * eps64 *
+    (1 + |q_0| + |g q_{nz-1}|)``, the rounding noise of the sum itself: a
+    singular periodic ``T`` (``b = -(a + c)``) has ``den = 0`` in real
+    arithmetic, which float64 returns as anything from 0 to about ``eps64``
+    depending on ``nz``."""
     def bad(k, pivot):
         return ValueError(
             f"the stencil is not positive definite along z: pivot {k} of "
@@ -81,7 +98,9 @@ def _thomas(nz, a, b, c, periodic):
             q[k] -= cp[k] * q[k + 1]
         g = a / gamma
         den = 1.0 + q[0] + g * q[-1]
-        if not (math.isfinite(den) and den > 0.0):
+        tiny = _SINGULAR * nz * sys.float_info.epsilon * (
+            1.0 + abs(q[0]) + abs(g * q[-1]))
+        if not (math.isfinite(den) and den > tiny):
             raise bad(nz, den)
         qs, lo[0] = [v / den for v in q], g
     return inv, cp, qs, lo

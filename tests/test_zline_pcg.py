@@ -8,13 +8,28 @@ Reference of a line solve: the dense float64 ``T`` and
 kappa``; the rest is margin for the rounded reciprocal tables.  The bands
 ``(-1.5, 3, -1)`` are diagonally dominant and not symmetric, so a swap of
 ``a`` and ``c`` shows.
+
+``TALL_CASES`` are the heights at which the native kernel (block of 4 rows
+x 64 columns, sweeps in batches of ``kZU = 4`` planes, at most 63 float32
+or 31 float64 planes of LDS stash) changes path: nz = 8 / 9 is two full
+batches and one plane more; 31 (float64) and 63 (float32) are the largest
+all-LDS launches; 32 and 64 put one plane through ``z`` (64 in float32 is
+the benchmark's launch) and end the column on a batch edge; 33 and 65 split
+the stash by default and have a ragged last batch.  Their planes are
+(5 + 2w) x (68 + 2w): 2 x 2 tiles, ragged both ways, at halo width w in
+1..3, so an origin or a tile grid offset by 1 instead of ``w`` lands in the
+halo.  The bands are ``BANDS``, the benchmark's ``(-100, 205, -100)`` and
+the weakly dominant ``(-1, 2.01, -1)`` (kappa of order 1e2 to 1e3).
+``UPDATE_CASES`` take the fused update to the same heights and to w = 2,
+and ``PCG_CASES`` run whole solves over two fields and two columns, a
+default split under periodic z, and w = 2.
 """
 
 import pytest
 import torch
 
 import mpi4jax_amd as m
-from mpi4jax_amd.parallel import StencilCG, StencilPCG, ZLineSolver
+from mpi4jax_amd.parallel import StencilCG, StencilPCG, ZLineSolver, zline
 from mpi4jax_amd.parallel.grid import CartesianGrid
 from test_halo_adjoint import int_data
 from test_halo_exchanger import PERIODIC
@@ -26,14 +41,59 @@ F32_F64 = (torch.float32, torch.float64)
 BANDS = (-1.5, 3.0, -1.0)
 NZS = {"zero": (1, 2, 3, 7), "periodic": (3, 7)}
 SOLVE_CASES = [(zb, nz) for zb in ZB for nz in NZS[zb]]
+BENCH = (-100.0, 205.0, -100.0)
+WEAK = (-1.0, 2.01, -1.0)
+_Z, _P, _F, _D = "zero", "periodic", torch.float32, torch.float64
+# (z boundary, nz, w, dtype, bands, batch): every nz at w = 1, every w at
+# nz = 33 and 65; batch = 2 runs two fields of (2, nz, ..) once per dtype
+TALL_CASES = [
+    (_Z, 8, 1, _F, BANDS, 0), (_P, 8, 1, _D, BENCH, 0),
+    (_P, 9, 1, _F, WEAK, 0), (_Z, 9, 1, _D, BANDS, 0),
+    (_Z, 31, 1, _D, BENCH, 0), (_P, 31, 1, _D, BANDS, 0),
+    (_P, 31, 1, _F, WEAK, 0),
+    (_P, 32, 1, _D, WEAK, 0), (_Z, 32, 1, _F, BANDS, 0),
+    (_Z, 33, 1, _D, BANDS, 0), (_P, 33, 1, _D, BENCH, 0),
+    (_Z, 33, 1, _F, WEAK, 0),
+    (_Z, 63, 1, _F, BENCH, 0), (_P, 63, 1, _F, BANDS, 0),
+    (_Z, 63, 1, _D, WEAK, 0),
+    (_P, 64, 1, _F, BENCH, 0), (_Z, 64, 1, _F, BANDS, 0),
+    (_P, 64, 1, _D, WEAK, 0),
+    (_Z, 65, 1, _F, WEAK, 0), (_P, 65, 1, _F, BANDS, 0),
+    (_P, 65, 1, _D, BENCH, 0),
+    (_P, 33, 2, _D, BANDS, 0), (_Z, 33, 2, _F, BENCH, 0),
+    (_Z, 65, 2, _F, BANDS, 0), (_P, 65, 2, _D, WEAK, 0),
+    (_Z, 33, 3, _D, WEAK, 0), (_P, 33, 3, _F, BANDS, 0),
+    (_P, 65, 3, _F, BENCH, 0), (_Z, 65, 3, _D, BANDS, 0),
+    (_P, 65, 2, _F, BANDS, 2), (_Z, 33, 1, _D, BENCH, 2),
+]
+# (shape, w, dtype) of the fused update beyond run_update's default
+UPDATE_CASES = [((2, 33, 7, 70), 1, _D), ((2, 65, 7, 70), 1, _F),
+                ((2, 9, 9, 72), 2, _F), ((2, 9, 9, 72), 2, _D)]
+# name: (dtype, z boundary, grid, fields, shape, w, rtol)
+PCG_CASES = {
+    "a": (_D, _Z, (True, True), 2, (2, 9, 14, 70), 1, 1e-10),
+    "b": (_F, _P, (False, True), 1, (33, 7, 70), 1, 1e-5),
+    "c": (_F, _Z, (False, False), 1, (9, 11, 74), 2, 1e-5),
+}
+SINGULAR = ((-1.0, 2.0, -1.0), (-0.5, 1.0, -0.5), (-100.0, 200.0, -100.0))
+NEARLY = (-1.0, 2.0 + 1e-6, -1.0)
 
 
-def weights(a, b, c, h=-0.25):
-    """Bands ``(a, b, c)`` along z and ``h`` on the four in-plane
-    neighbours."""
-    k = torch.zeros(3, 3, 3, dtype=torch.float64)
-    k[0, 1, 1], k[1, 1, 1], k[2, 1, 1] = a, b, c
-    k[1, 0, 1] = k[1, 2, 1] = k[1, 1, 0] = k[1, 1, 2] = h
+def case_id(v):
+    if isinstance(v, torch.dtype):
+        return str(v)[6:]
+    if isinstance(v, tuple):
+        return "x".join(case_id(e) or str(e) for e in v)
+    return None
+
+
+def weights(a, b, c, h=-0.25, w=1):
+    """Bands ``(a, b, c)`` along z and ``h`` on the in-plane star out to
+    distance ``w``: a 3 x (2w+1) x (2w+1) table, halo width ``w``."""
+    k = torch.zeros(3, 2 * w + 1, 2 * w + 1, dtype=torch.float64)
+    k[0, w, w], k[1, w, w], k[2, w, w] = a, b, c
+    for d in range(1, w + 1):
+        k[1, w - d, w] = k[1, w + d, w] = k[1, w, w - d] = k[1, w, w + d] = h
     return k
 
 
@@ -47,21 +107,30 @@ def dense_t(nz, a, b, c, zb):
     return t
 
 
-def check_solution(z, r, t, dtype, what):
-    """``z`` against ``T^{-1} r`` on the interior (w = 1), its halo zero;
-    returns the error over ``eps kappa``."""
+def kappa_inf(t):
+    return (torch.linalg.matrix_norm(t, float("inf"))
+            * torch.linalg.matrix_norm(torch.linalg.inv(t), float("inf")))
+
+
+def clip_lds(lds, nz, dtype):
+    """``lds`` clipped to what ``_lds_planes`` accepts; None stays."""
+    return lds and min(lds, nz, zline.MAX_LDS // (zline.BLOCK
+                                                  * dtype.itemsize))
+
+
+def check_solution(z, r, t, dtype, what, w=1):
+    """``z`` against ``T^{-1} r`` on the interior at width ``w``, its halo
+    zero; returns the error over ``eps kappa``."""
     nz = t.shape[0]
-    ri = interior(r.cpu().double(), 1)
+    ri = interior(r.cpu().double(), w)
     ref = torch.linalg.solve(
         t, ri.reshape(-1, nz, ri.shape[-2] * ri.shape[-1]))
-    got = interior(z.cpu().double(), 1).reshape(ref.shape)
-    kappa = (torch.linalg.matrix_norm(t, float("inf"))
-             * torch.linalg.matrix_norm(torch.linalg.inv(t), float("inf")))
+    got = interior(z.cpu().double(), w).reshape(ref.shape)
     ratio = ((got - ref).abs().max() / ref.abs().max()
-             / (torch.finfo(dtype).eps * kappa)).item()
+             / (torch.finfo(dtype).eps * kappa_inf(t))).item()
     assert ratio <= 16.0, (what, ratio)
     halo = z.clone()
-    interior(halo, 1).zero_()
+    interior(halo, w).zero_()
     assert not halo.any(), (what, "halo written")
     return ratio
 
@@ -91,11 +160,36 @@ def run_solve(grids, zb, nz, dtype, device, lds=None):
     return worst, outs
 
 
-def run_update(grid, zb, dtype, device, lds=None):
+def run_tall(grid, case, device, lds=None):
+    """``solve`` of one row of ``TALL_CASES``; returns the ratio and the
+    outputs."""
+    zb, nz, w, dtype, bands, batch = case
+    shape = (nz, 5 + 2 * w, 68 + 2 * w)
+    nf = 1
+    if batch:
+        shape, nf = (batch,) + shape, 2
+    t = dense_t(nz, *bands, zb)
+    st = grid.make_stencil3d(shape, dtype, device, weights(*bands, w=w),
+                             nfields=nf, z_boundary=zb)
+    ls = st.make_line_solver(_lds_planes=clip_lds(lds, nz, dtype))
+    assert ls.bands == bands and st.width == w
+    g = torch.Generator().manual_seed(nz + w)
+    r = [torch.randn(shape, generator=g, dtype=torch.float64).to(dtype)
+         .to(device) for _ in range(nf)]
+    keep = [f.clone() for f in r]
+    z = as_tuple(ls.solve(*r))
+    worst = 0.0
+    for fz, fr, fk in zip(z, r, keep):
+        assert torch.equal(fr, fk), "solve() mutated its input"
+        worst = max(worst, check_solution(fz, fr, t, dtype, (case, lds), w))
+    return worst, [f.cpu() for f in z]
+
+
+def run_update(grid, zb, dtype, device, lds=None, shape=(2, 7, 41, 70), w=1):
     """One fused update against ``StencilCG.update_step`` and the dense
     solve, on integer data with ``alpha = 2``."""
-    shape, nf, w = (2, 7, 41, 70), 2, 1
-    st = grid.make_stencil3d(shape, dtype, device, weights(*BANDS),
+    nf = 2
+    st = grid.make_stencil3d(shape, dtype, device, weights(*BANDS, w=w),
                              nfields=nf, z_boundary=zb)
     cg, pcg, again = st.make_cg(), st.make_cg("zline", _lds_planes=lds), \
         st.make_cg("zline", _lds_planes=lds)
@@ -115,10 +209,10 @@ def run_update(grid, zb, dtype, device, lds=None):
     assert pcg.rr.item() == sum(int_dot(interior(f, w), interior(f, w))
                                 for f in pcg._r)
     assert pcg.rz_old.item() == 4.0
-    t = dense_t(7, *BANDS, zb)
+    t = dense_t(shape[-3], *BANDS, zb)
     zs = as_tuple(pcg.preconditioned_residual)
     for fz, fr in zip(zs, pcg._r):
-        check_solution(fz, fr, t, dtype, (zb, dtype, lds))
+        check_solution(fz, fr, t, dtype, (zb, dtype, lds, shape), w)
     assert pcg.rz.item() == pytest.approx(st.dot(pcg._r, zs).item(),
                                           rel=1e-12)
     for a, b in zip(zs + (pcg.rz,), as_tuple(again.preconditioned_residual)
@@ -156,6 +250,32 @@ def run_anisotropic(grid, device, rtol=1e-5):
     return info.iterations, plain.iterations
 
 
+def run_pcg(grids, name, device):
+    """One row of ``PCG_CASES``: vertical weight 100, horizontal 1, the
+    centre 1 above the sum of the others.  Accepted as the project's own
+    solves are: ``converged``, and the true residual of the float64 oracle
+    within ``10 rtol``.  Returns the iteration count."""
+    dtype, zb, periodic, nf, shape, w, rtol = PCG_CASES[name]
+    k = weights(-100.0, 201.0 + 4 * w, -100.0, h=-1.0, w=w)
+    g = torch.Generator().manual_seed(11)
+    b = [torch.nn.functional.pad(
+        interior(torch.randn(shape, generator=g, dtype=torch.float64), w),
+        (w,) * 4).to(dtype).to(device) for _ in range(nf)]
+    st = grids[periodic].make_stencil3d(shape, dtype, device, k, nfields=nf,
+                                        z_boundary=zb)
+    x, info = st.make_cg("zline").solve(b if nf > 1 else b[0], rtol=rtol,
+                                        maxiter=200, check_every=1)
+    assert info.converged is True, (name, info)
+    num = den = 0.0
+    for fb, ax in zip(b, oracle(grids[periodic], k, as_tuple(x), zb)):
+        bi = interior(fb.cpu().double(), w)
+        num, den = num + (bi - ax).pow(2).sum(), den + bi.pow(2).sum()
+    true = (num / den).sqrt().item()
+    print("pcg", name, device, "iterations", info.iterations, "true", true)
+    assert true <= 10 * rtol, (name, true)
+    return info.iterations
+
+
 @pytest.fixture(scope="module")
 def grids():
     m.init()
@@ -186,6 +306,57 @@ def test_update_matches_composition(grids, zb, dtype):
 
 def test_pcg_halves_the_iterations(grids):
     run_anisotropic(grids[(False, False)], "cpu")
+
+
+@pytest.mark.parametrize("case", TALL_CASES, ids=case_id)
+def test_tall_wide_line_solve_matches_dense(grids, case):
+    print("err / (eps kappa):",
+          run_tall(grids[(True, True)], case, "cpu")[0])
+
+
+@pytest.mark.parametrize("zb", ZB)
+@pytest.mark.parametrize("shape,w,dtype", UPDATE_CASES, ids=case_id)
+def test_update_matches_composition_at_height(grids, shape, w, dtype, zb):
+    run_update(grids[(True, True)], zb, dtype, "cpu", shape=shape, w=w)
+
+
+@pytest.mark.parametrize("name", PCG_CASES)
+def test_pcg_end_to_end(grids, name):
+    run_pcg(grids, name, "cpu")
+
+
+def test_singular_periodic_bands_are_refused(grids):
+    """Periodic ``T`` with ``b = -(a + c)`` is singular at every height:
+    the Sherman-Morrison denominator is 0 in real arithmetic, and between
+    0 and eps in float64.  ``b`` larger by 1e-6 is accepted and solves to
+    the dense reference within ``16 eps kappa`` (kappa is about 4e6)."""
+    grid = grids[(True, True)]
+
+    def make(nz, bands):
+        return grid.make_stencil3d((nz, 3, 4), torch.float64, "cpu",
+                                   weights(*bands), z_boundary="periodic")
+
+    def accepts(st):
+        try:
+            st.make_line_solver()
+        except ValueError as e:
+            assert "not positive definite along z" in str(e)
+            return False
+        return True
+
+    accepted = [(nz, bands) for nz in range(3, 71) for bands in SINGULAR
+                if accepts(make(nz, bands))]
+    assert not accepted, accepted
+    for nz in range(3, 71):
+        ls = make(nz, NEARLY).make_line_solver()
+        assert torch.isfinite(ls.tables).all()
+        if nz in (3, 33, 65):
+            r = torch.randn(nz, 3, 4, dtype=torch.float64,
+                            generator=torch.Generator().manual_seed(nz))
+            ratio = check_solution(
+                ls.solve(r), r, dense_t(nz, *NEARLY, "periodic"),
+                torch.float64, ("nearly singular", nz))
+            print("nz", nz, "err / (eps kappa):", ratio)
 
 
 def test_errors(grids):
