@@ -632,7 +632,12 @@ void sw_stage(int64_t stage, std::vector<at::Tensor> bufs, double dx,
               double cor_dj, double ab_a, double ab_b,
               std::vector<int64_t> flags) {
   TORCH_CHECK(bufs.size() == 16, "sw_stage expects 16 buffers");
-  TORCH_CHECK(flags.size() == 7, "sw_stage expects 7 flags");
+  // an 8th entry sets how many fast tiles a block of the single-launch
+  // step marches through (stages 30/31); absent or 0 = the default
+  TORCH_CHECK(flags.size() == 7 || flags.size() == 8,
+              "sw_stage expects 7 flags (8 with a march length)");
+  TORCH_CHECK(flags.size() == 7 || (flags[7] >= 0 && flags[7] <= 1 << 20),
+              "sw_stage: bad march length ", flags.size() == 8 ? flags[7] : 0);
   const at::Tensor& h = bufs[4];
   TORCH_CHECK(h.is_cuda() && h.is_contiguous() && h.dim() == 2,
               "bad shallow-water state tensor");
@@ -667,6 +672,7 @@ void sw_stage(int64_t stage, std::vector<at::Tensor> bufs, double dx,
   p.east_wall = (int)flags[4];
   p.north_wall = (int)flags[5];
   p.x_wrap = (int)flags[6];
+  p.march = flags.size() == 8 ? (int)flags[7] : 0;
   const SwStageStatus rc =
       launch_sw_stage((int)stage, p, is_double ? 1 : 0, cur_stream());
   TORCH_CHECK(rc != SW_STAGE_UNKNOWN, "sw_stage: unknown stage id ", stage,

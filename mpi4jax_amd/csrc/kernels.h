@@ -56,6 +56,9 @@ struct SwLaunchParams {
   int south_open, north_open, west_open, east_open;
   int east_wall, north_wall;
   int x_wrap;  // x halos are LOCAL periodic wraps (nproc_x==1), not remote
+  // SW_STEP1 / SW_STEP1_512: the most fast tiles of one tile column that a
+  // block marches through; 0 = the launcher's default
+  int march;
 };
 
 // Launchable stage ids.  The values are public: profiles/ and the docs

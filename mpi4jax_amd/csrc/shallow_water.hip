@@ -31,23 +31,13 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "sw_tiles.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
-// XCD-aware block mapping: the dispatcher places block b on XCD b%8, so a
-// plain row-major grid scatters adjacent rows across XCDs and every j±1
-// stencil read misses that XCD's L2.  This bijective remap of block b of
-// T gives each XCD a contiguous band of ids, so neighbor rows are
-// L2-resident (MI355X_MICROARCH.md §Workgroup dispatch; speed-only).
-// (B = unsigned where the caller has b >= 0 from a branch: shift, no fix-up)
-template <typename B>
-__host__ __device__ inline int xcd_band_id(B b, int T) {
-  const int q8_ = T / 8, r8_ = T % 8, xc_ = b % 8, yc_ = b / 8;
-  return (xc_ < r8_ ? xc_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xc_ - r8_) * q8_)
-         + yc_;
-}
+// (xcd_band_id, the XCD-aware block remap, lives in sw_tiles.h)
 
 // one cell per thread: block -> (row j, 256-column chunk), so a wave64's
 // lanes touch consecutive columns (fully coalesced)
@@ -62,17 +52,6 @@ __host__ __device__ inline int xcd_band_id(B b, int T) {
 // float32 rounding of 9.81 (relative error 4e-8 in the pressure gradient).
 constexpr double kGravity = 9.81;
 constexpr float G = 9.81f;  // == (float)kGravity, float-only kernels
-
-struct SwFlags {
-  // "open" = this halo receives neighbor data (exchange or periodic wrap)
-  int south_open, north_open, west_open, east_open;
-  // physical walls (reference shallow_water.py:258-262): u column nx-2
-  // zeroed on a closed east edge, v row ny-2 zeroed on the north edge
-  int east_wall, north_wall;
-  // x halos are LOCAL periodic wraps (nproc_x == 1 && periodic), not
-  // remote exchanges — lets the fused ring kernel synthesize them
-  int x_wrap;
-};
 
 template <typename T>
 struct SwArgs {
@@ -99,19 +78,10 @@ struct SwArgs {
   T cor_base, cor_dj;  // coriolis(j) = cor_base + j * cor_dj
   T ab_a, ab_b;        // Adams-Bashforth coefficients (b=0 -> Euler)
   SwFlags f;
+  int march;  // sw_step1t: most fast tiles of a tile column per block
 };
 
-// The fast region: cells [jmin, jmax] x [imin, imax) whose whole stencil
-// is mask-free (open halos readable, no wall row/column, no hc clamp), so
-// the vector kernels run the plain formulas there; each adds its own
-// pack-width terms to the test.  Declares the four bounds as locals (a
-// macro like SW_BLOCK_MAP, not a struct: every struct or function form
-// tried changed the register allocation of the vector kernels).
-#define SW_FAST_BOUNDS(ny, nx, f)                                          \
-  const int jmin = (f).south_open ? 1 : 2;                                 \
-  const int jmax = ((f).north_open && !(f).north_wall) ? ny - 2 : ny - 3;  \
-  const int imin = (f).west_open ? 1 : 2;                                  \
-  const int imax = ((f).east_open && !(f).east_wall) ? nx - 1 : nx - 2
+// (SW_FAST_BOUNDS, the mask-free region, lives in sw_tiles.h)
 
 // hc = h padded by edge replication at closed halos (reference
 // shallow_water.py:278-279 + enforce_boundaries); at open halos hc == h.
@@ -1112,8 +1082,7 @@ __device__ inline void s30_read_uv(const SwArgs<float>& a, int jj, int ii,
 // kernel at stage 19's VGPR budget (70 -> 7 waves/SIMD).  Store
 // partition between the kernels is exact and index-only: dn*/h2 by
 // stage19_pair_fast, u2/v2 by s30_fast_out.
-constexpr int kTJ30 = 14;    // output rows per block
-constexpr int kPC30 = 30;    // output pairs (2 cols) per row
+// (kTJ30 = 14 output rows, kPC30 = 30 output pairs per row: sw_tiles.h)
 constexpr int kTR30 = kTJ30 + 2;           // tile rows
 constexpr int kTP30 = kPC30 + 2;           // tile pairs per row
 constexpr int kFill30 = kTR30 * kTP30;     // LDS fill tasks
@@ -1132,19 +1101,25 @@ __host__ __device__ inline bool s30_fast_out(const SwArgs<float>& a, int j,
 typedef float S30Tile[kTR30][2 * kTP30];
 
 // friction of the output pair at LDS tile row lr, column x, from the
-// post-update u'/v' tile
+// post-update u'/v' tile; ls / ln are the LDS rows holding the field rows
+// below and above (lr -+ 1, unless the tile's rows are rotated)
 __device__ inline UV2 s30_friction_lds(const SwArgs<float>& a,
                                        const S30Tile& su, const S30Tile& sv,
-                                       int lr, int x) {
+                                       int ls, int lr, int ln, int x) {
   return friction_pair(
       a, (vf2){su[lr][x - 1], su[lr][x]}, (vf2){su[lr][x], su[lr][x + 1]},
       (vf2){su[lr][x + 1], su[lr][x + 2]},
-      (vf2){su[lr + 1][x], su[lr + 1][x + 1]},
-      (vf2){su[lr - 1][x], su[lr - 1][x + 1]},
+      (vf2){su[ln][x], su[ln][x + 1]},
+      (vf2){su[ls][x], su[ls][x + 1]},
       (vf2){sv[lr][x - 1], sv[lr][x]}, (vf2){sv[lr][x], sv[lr][x + 1]},
       (vf2){sv[lr][x + 1], sv[lr][x + 2]},
-      (vf2){sv[lr + 1][x], sv[lr + 1][x + 1]},
-      (vf2){sv[lr - 1][x], sv[lr - 1][x + 1]});
+      (vf2){sv[ln][x], sv[ln][x + 1]},
+      (vf2){sv[ls][x], sv[ls][x + 1]});
+}
+__device__ inline UV2 s30_friction_lds(const SwArgs<float>& a,
+                                       const S30Tile& su, const S30Tile& sv,
+                                       int lr, int x) {
+  return s30_friction_lds(a, su, sv, lr - 1, lr, lr + 1, x);
 }
 
 template <int NT_>
@@ -1339,77 +1314,16 @@ __global__ void sw_stage30_ringB(SwArgs<float> a) {
 // the tile) so no wave of mostly-fast pairs diverges into scalar code.
 // Ownership of every store stays predicate-defined; the enumeration only
 // decides which threads look.
+//
+// A block owns one perimeter tile, or a segment of up to `march` fast
+// tiles of one tile column (SwArgs::march, a runtime value; sw_tiles.h
+// has the split).  It walks the segment from the low tile row up
+// (s1_fast_march): the rows two tiles share stay in LDS and the next
+// tile's new window rows are prefetched.  The result does not depend on
+// the march length, bit for bit.  The default is 1, one tile per block:
+// longer marches measured slower (profiles/README.md).
 
-// the fast tiles form a rectangle [tr0, tr1] x [tc0, tc1] of the tile
-// grid (both predicates are pure bounds); host and device share this
-struct S1Tiles {
-  int bpc, bands, tr0, tr1, tc0, tc1, nfast, nper, nper_pad;
-};
-
-__host__ __device__ inline int s1_floordiv(int x, int d) {
-  return x >= 0 ? x / d : -((-x + d - 1) / d);
-}
-
-__host__ __device__ inline S1Tiles s1_tiles(int ny, int nx,
-                                            const SwFlags& f) {
-  SW_FAST_BOUNDS(ny, nx, f);
-  S1Tiles t;
-  t.bpc = (nx + 2 * kPC30 - 1) / (2 * kPC30);
-  t.bands = (ny + kTJ30 - 1) / kTJ30;
-  // rows jb-1 .. jb+TJ all stage19-fast; pairs cb-2 .. cb+2*PC all
-  // stage19-fast (i0 + 2 <= imax, i0 + 3 < nx at the last fill pair)
-  t.tr0 = s1_floordiv(jmin + 1 + kTJ30 - 1, kTJ30);
-  t.tr1 = s1_floordiv(jmax - kTJ30, kTJ30);
-  t.tc0 = s1_floordiv(imin + 2 + 2 * kPC30 - 1, 2 * kPC30);
-  const int ihi = imax - 2 < nx - 4 ? imax - 2 : nx - 4;
-  t.tc1 = s1_floordiv(ihi - 2 * kPC30, 2 * kPC30);
-  if (t.tr1 > t.bands - 1) t.tr1 = t.bands - 1;
-  if (t.tc1 > t.bpc - 1) t.tc1 = t.bpc - 1;
-  const bool any = t.tr0 <= t.tr1 && t.tc0 <= t.tc1;
-  t.nfast = any ? (t.tr1 - t.tr0 + 1) * (t.tc1 - t.tc0 + 1) : 0;
-  if (!any) {  // canonical empty rectangle: every band is a "top" band
-    t.tr0 = t.bands;
-    t.tr1 = t.bands - 1;
-    t.tc0 = 0;
-    t.tc1 = -1;
-  }
-  t.nper = t.bpc * t.bands - t.nfast;
-  // the dispatcher deals blocks to XCDs by raw id mod 8: pad so the fast
-  // tiles' XCD bands start on a multiple of 8
-  t.nper_pad = (t.nper + 7) / 8 * 8;
-  return t;
-}
-
-// block id -> tile.  Perimeter tiles take the lowest block ids, so their
-// longer scalar chains overlap the bulk instead of forming a tail; the
-// fast tiles keep the XCD-band remap over their own rectangle.  Returns
-// 0 for a padding block, 1 for a perimeter tile, 2 for a fast tile.
-__host__ __device__ inline int s1_block_tile(const S1Tiles& tl, int b,
-                                             int* tr, int* tc) {
-  if (b < tl.nper_pad) {
-    if (b >= tl.nper) return 0;
-    const int top = tl.tr0 * tl.bpc;
-    const int bot = (tl.bands - 1 - tl.tr1) * tl.bpc;
-    if (b < top) {
-      *tr = b / tl.bpc;
-      *tc = b % tl.bpc;
-    } else if (b < top + bot) {
-      *tr = tl.tr1 + 1 + (b - top) / tl.bpc;
-      *tc = (b - top) % tl.bpc;
-    } else {
-      const int w = tl.tc0 + (tl.bpc - 1 - tl.tc1);
-      const int u = b - top - bot, c = u % w;
-      *tr = tl.tr0 + u / w;
-      *tc = c < tl.tc0 ? c : tl.tc1 + 1 + (c - tl.tc0);
-    }
-    return 1;
-  }
-  const int bid_ = xcd_band_id((unsigned)(b - tl.nper_pad), tl.nfast);
-  const int fw = tl.tc1 - tl.tc0 + 1;
-  *tr = tl.tr0 + bid_ / fw;
-  *tc = tl.tc0 + bid_ % fw;
-  return 2;
-}
+// (S1Tiles, s1_tiles and s1_block_tile live in sw_tiles.h)
 
 // a tile's fast cells as a local rectangle: rows [r0, r1] x cols
 // [c0, c1] of an R-row x 2P-column grid, from the first/last fast local
@@ -1514,13 +1428,28 @@ constexpr int kWLoads = kWLd4 + kWR30;   // + one 2-wide position per row
 typedef float S1Win[3][kWR30][kWC30];  // h, u, v
 typedef float lf2 __attribute__((ext_vector_type(2)));  // 8-byte aligned
 
-// pass 1 of a fast tile: the stage-19 update of all 16 x 32 fill pairs
-// from the staged window, into the u'/v' tile and the owned outputs
+// A block owns a segment of `ntile` fast tiles of one tile column and
+// marches up it.  Consecutive tiles share 4 window rows (rows jb+12 ..
+// jb+15 of the lower tile) and 2 fill rows (jb+13, jb+14): both stay in
+// LDS, whose rows are indexed modulo 18 (window) and 16 (u'/v' tile), so a
+// following tile loads 14 window rows and computes 14 fill rows.  Those
+// are the fill tasks from kMarchT0 on, so a following tile runs the first
+// tile's task loop from a later start.  Its window rows are one load
+// position per thread:
+constexpr int kMarchT0 = 2 * kTP30;         // first fill task, later tiles
+constexpr int kMLd4 = kTJ30 * kWQ30;        // 4-wide load positions
+constexpr int kMLoads = kMLd4 + kTJ30;      // + one 2-wide position per row
+
+// a fast segment: per tile, pass 1 (the stage-19 update of the fill pairs
+// from the staged window, into the u'/v' tile and the owned outputs) and
+// pass 2 (friction of the output pairs from the u'/v' tile)
 template <int NT_>
-__device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
-                                    int tid, S1Win& win, S30Tile& su,
-                                    S30Tile& sv) {
+__device__ inline void s1_fast_march(const SwArgs<float>& a, int jb, int cb,
+                                     int ntile, int tid0, S1Win& win,
+                                     S30Tile& su, S30Tile& sv) {
   static_assert(kFill30 % NT_ == 0, "whole fill rounds");
+  static_assert(kMLoads <= NT_, "one prefetch position per thread");
+  static_assert(kMarchT0 % 64 == 0, "whole waves skip a later tile's tasks");
   constexpr int kRounds = (kWLoads + NT_ - 1) / NT_;
   constexpr int kTasks = kFill30 / NT_;
   const int nx = (int)a.nx;
@@ -1539,7 +1468,7 @@ __device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
   vf4 wh[kRounds], wu[kRounds], wv[kRounds];
 #pragma unroll
   for (int k = 0; k < kRounds; ++k) {
-    const int t = tid + k * NT_;
+    const int t = tid0 + k * NT_;
     if ((k + 1) * NT_ <= kWLd4 || t < kWLd4) {
       const long long o = org + (t / kWQ30 * nx + t % kWQ30 * 4);
       wh[k] = ld4(a.h, o);
@@ -1553,22 +1482,31 @@ __device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
       wv[k] = (vf4){xv.x, xv.y, 0.f, 0.f};
     }
   }
-  // the old tendencies stay in global memory; an apron pair's h update
-  // is discarded, so it skips doh
-  vf2 doh[kTasks], dou[kTasks], dov[kTasks];
-#pragma unroll
-  for (int k = 0; k < kTasks; ++k) {
-    const int t = tid + k * NT_;
+  // March state.  t0: the tile's first fill task.  wrot / frot: LDS row
+  // of window row 0 / fill row 0.  lown: the last fill row whose pair the
+  // block stores.  That is the tile's last output row; below another tile
+  // of the segment it is the fill row above it too, which is the next
+  // tile's first output row and is not computed again there.
+  int t0 = 0, wrot = 0, frot = 0;
+  int lown = ntile > 1 ? kTJ30 + 1 : kTJ30;
+  // The old tendencies stay in global memory; an apron pair's h update
+  // is discarded, so it skips doh.  A thread holds one task's tendencies:
+  // the first task's are requested with the window, a following task's
+  // when the task before it ends, and a task reads them last of all.
+  vf2 toh, tou, tov;
+  auto load_tendencies = [&](int t) {
     const int lr = t / kTP30, lp = t % kTP30;
     const long long idx = (long long)(jb - 1 + lr) * nx + (cb - 2 + 2 * lp);
-    const bool owned = lr >= 1 && lr <= kTJ30 && lp >= 1 && lp <= kPC30;
-    dou[k] = ld2(a.dou, idx);
-    dov[k] = ld2(a.dov, idx);
-    doh[k] = owned ? ld2(a.doh, idx) : (vf2){0.f, 0.f};
-  }
+    const bool live = t < kFill30;  // a later tile has fewer tasks
+    const bool owned = lr >= 1 && lr <= lown && lp >= 1 && lp <= kPC30;
+    tou = live ? ld2(a.dou, idx) : (vf2){0.f, 0.f};
+    tov = live ? ld2(a.dov, idx) : (vf2){0.f, 0.f};
+    toh = live && owned ? ld2(a.doh, idx) : (vf2){0.f, 0.f};
+  };
+  load_tendencies(tid0);
 #pragma unroll
   for (int k = 0; k < kRounds; ++k) {
-    const int t = tid + k * NT_;
+    const int t = tid0 + k * NT_;
     if ((k + 1) * NT_ <= kWLd4 || t < kWLd4) {
       const int r = t / kWQ30, c = t % kWQ30 * 4;
       *(lf2*)&win[0][r][c] = (lf2){wh[k].x, wh[k].y};
@@ -1584,9 +1522,9 @@ __device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
       *(lf2*)&win[2][r][c] = (lf2){wv[k].x, wv[k].y};
     }
   }
-  __syncthreads();
 
-  // columns i0-1 .. i0+2 of window row wr, i0 the first column of pair lp
+  // columns i0-1 .. i0+2 of LDS window row wr, i0 the first column of
+  // pair lp
   auto row4 = [&](int f, int wr, int lp) -> vf4 {
     const lf2 p = *(const lf2*)&win[f][wr][2 * lp];
     const lf2 q = *(const lf2*)&win[f][wr][2 * lp + 2];
@@ -1597,54 +1535,135 @@ __device__ inline void s1_fast_fill(const SwArgs<float>& a, int jb, int cb,
     const vf4 A = row4(f, wr, lp);
     return (vf4){A.y, A.z, A.w, A.w};
   };
-  // A rolled loop: every fill task runs the one compiled body.  Unrolled,
-  // the compiler contracts the second task's expressions to FMA
-  // differently from the first's, and the 256-thread kernel (two tasks
-  // per thread) no longer equals the 512-thread one (one task) bitwise.
-  static_assert(kTasks <= 2, "the loop carries one task's tendencies");
-  vf2 toh = doh[0], tou = dou[0], tov = dov[0];
+  auto wrap = [](int r, int n) { return r >= n ? r - n : r; };
+
+  // One rolled loop over the segment's tiles, so that every tile, first
+  // or later, runs the one compiled fill body and friction body.
 #pragma unroll 1
-  for (int k = 0; k < kTasks; ++k) {
-    const int t = tid + k * NT_;
-    const int lr = t / kTP30, lp = t % kTP30;
-    const int rr = jb - 1 + lr;  // window row lr is field row rr - 1
-    const vf4 H0A = row4(0, lr + 1, lp), U0A = row4(1, lr + 1, lp),
-              V0A = row4(2, lr + 1, lp);
-    Upd2 r = stage19_update(
-        a, rr, row4p(0, lr, lp), H0A, row4(0, lr + 2, lp),
-        x01(row4p(1, lr, lp)), U0A, row4(1, lr + 2, lp), row4p(2, lr, lp),
-        V0A, x01(row4p(2, lr + 2, lp)), toh, tou, tov);
-    // the AB time update with its rounding spelled out (see
-    // s1_ab_update_fused): left to the compiler, the 256- and 512-thread
-    // instantiations contract it differently from each other and from
-    // the global-load fill
-    r.hh = s1_ab_update_fused(x12(H0A), a.dt, a.ab_b, toh, a.ab_a, r.dnh);
-    r.uu = s1_ab_update_fused(x12(U0A), a.dt, a.ab_a, r.dnu, a.ab_b, tou);
-    r.vv = s1_ab_update_fused(x12(V0A), a.dt, a.ab_a, r.dnv, a.ab_b, tov);
-    su[lr][2 * lp] = r.uu.x;
-    su[lr][2 * lp + 1] = r.uu.y;
-    sv[lr][2 * lp] = r.vv.x;
-    sv[lr][2 * lp + 1] = r.vv.y;
-    if (lr >= 1 && lr <= kTJ30 && lp >= 1 && lp <= kPC30) {
-      const long long idx = (long long)rr * nx + (cb - 2 + 2 * lp);
-      st2(a.dnh, idx, r.dnh);
-      st2(a.dnu, idx, r.dnu);
-      st2(a.dnv, idx, r.dnv);
-      st2(a.h2, idx, r.hh);
+  for (int m = 0;; ++m) {
+    // The thread id, taken afresh for every tile through an empty asm the
+    // compiler cannot see through.  Otherwise it computes every index and
+    // address that depends on the thread alone once before the loop and
+    // keeps them all in registers: 103 VGPRs, 4 waves per SIMD, not 91
+    // and 5.
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    __syncthreads();  // the window is staged; the u'/v' tile is free
+    const bool more = m + 1 < ntile;
+
+    // Prefetch: the 14 window rows the next tile adds (its rows jb+16 ..
+    // jb+29) are requested before this tile's math and land in LDS after
+    // its friction pass.  The next tile is a fast tile, so the bounds
+    // argument above holds for its window.
+    vf4 ph, pu, pv;
+    if (more && tid < kMLoads) {
+      const long long porg = (long long)(jb + kTR30) * nx + (cb - 3);
+      if (tid < kMLd4) {
+        const long long o = porg + (tid / kWQ30 * nx + tid % kWQ30 * 4);
+        ph = ld4(a.h, o);
+        pu = ld4(a.u, o);
+        pv = ld4(a.v, o);
+      } else {
+        const long long o = porg + ((tid - kMLd4) * nx + 4 * kWQ30);
+        // lanes z, w stay unset and unread: writing them here would make
+        // the wave wait for the loads it has just issued
+        const vf2 xh = ld2(a.h, o), xu = ld2(a.u, o), xv = ld2(a.v, o);
+        ph.x = xh.x, ph.y = xh.y;
+        pu.x = xu.x, pu.y = xu.y;
+        pv.x = xv.x, pv.y = xv.y;
+      }
     }
-    toh = doh[kTasks - 1];
-    tou = dou[kTasks - 1];
-    tov = dov[kTasks - 1];
+
+    // A rolled loop: every fill task runs the one compiled body.
+    // Unrolled, the compiler contracts the second task's expressions to
+    // FMA differently from the first's, and the 256-thread kernel (two
+    // tasks per thread) no longer equals the 512-thread one (one task)
+    // bitwise.
+#pragma unroll 1
+    for (int k = 0; k < kTasks; ++k) {
+      const int t = tid + t0 + k * NT_;
+      if (t < kFill30) {
+        const int lr = t / kTP30, lp = t % kTP30;
+        const int rr = jb - 1 + lr;  // window row lr is field row rr - 1
+        const int w0 = wrap(lr + wrot, kWR30), w1 = wrap(w0 + 1, kWR30),
+                  w2 = wrap(w1 + 1, kWR30);
+        const int fr = (lr + frot) % kTR30;
+        const vf4 H0A = row4(0, w1, lp), U0A = row4(1, w1, lp),
+                  V0A = row4(2, w1, lp);
+        Upd2 r = stage19_update(
+            a, rr, row4p(0, w0, lp), H0A, row4(0, w2, lp),
+            x01(row4p(1, w0, lp)), U0A, row4(1, w2, lp), row4p(2, w0, lp),
+            V0A, x01(row4p(2, w2, lp)), toh, tou, tov);
+        // the AB time update with its rounding spelled out (see
+        // s1_ab_update_fused): left to the compiler, the 256- and
+        // 512-thread instantiations contract it differently from each
+        // other and from the global-load fill
+        r.hh = s1_ab_update_fused(x12(H0A), a.dt, a.ab_b, toh, a.ab_a,
+                                  r.dnh);
+        r.uu = s1_ab_update_fused(x12(U0A), a.dt, a.ab_a, r.dnu, a.ab_b,
+                                  tou);
+        r.vv = s1_ab_update_fused(x12(V0A), a.dt, a.ab_a, r.dnv, a.ab_b,
+                                  tov);
+        su[fr][2 * lp] = r.uu.x;
+        su[fr][2 * lp + 1] = r.uu.y;
+        sv[fr][2 * lp] = r.vv.x;
+        sv[fr][2 * lp + 1] = r.vv.y;
+        if (lr >= 1 && lr <= lown && lp >= 1 && lp <= kPC30) {
+          const long long idx = (long long)rr * nx + (cb - 2 + 2 * lp);
+          st2(a.dnh, idx, r.dnh);
+          st2(a.dnu, idx, r.dnu);
+          st2(a.dnv, idx, r.dnv);
+          st2(a.h2, idx, r.hh);
+        }
+      }
+      if (k + 1 < kTasks) load_tendencies(t + NT_);
+    }
+    __syncthreads();  // the u'/v' tile is complete; the window is free
+
+    // pass 2: friction of the output pairs from LDS.  Every output pair
+    // of a fast tile is s30_fast_out.
+    for (int t = tid; t < kTJ30 * kPC30; t += NT_) {
+      const int ro = t / kPC30, po = t % kPC30;
+      const long long idx = (long long)(jb + ro) * nx + (cb + 2 * po);
+      const int ls = (ro + frot) % kTR30, lr = (ls + 1) % kTR30,
+                ln = (lr + 1) % kTR30;
+      const UV2 r = s30_friction_lds(a, su, sv, ls, lr, ln, 2 * po + 2);
+      st2(a.u2, idx, r.u);
+      st2(a.v2, idx, r.v);
+    }
+    if (!more) break;
+
+    // step to the next tile: the 4 window rows and 2 fill rows it shares
+    // with this one become its first rows
+    jb += kTJ30;
+    t0 = kMarchT0;
+    wrot = wrap(wrot + kTJ30, kWR30);
+    frot = (frot + kTJ30) % kTR30;
+    lown = m + 2 < ntile ? kTJ30 + 1 : kTJ30;
+    load_tendencies(tid + t0);
+    if (tid < kMLoads) {
+      const int r = wrap(
+          (tid < kMLd4 ? tid / kWQ30 : tid - kMLd4) + 4 + wrot, kWR30);
+      const int c = tid < kMLd4 ? tid % kWQ30 * 4 : 4 * kWQ30;
+      *(lf2*)&win[0][r][c] = (lf2){ph.x, ph.y};
+      *(lf2*)&win[1][r][c] = (lf2){pu.x, pu.y};
+      *(lf2*)&win[2][r][c] = (lf2){pv.x, pv.y};
+      if (tid < kMLd4) {
+        *(lf2*)&win[0][r][c + 2] = (lf2){ph.z, ph.w};
+        *(lf2*)&win[1][r][c + 2] = (lf2){pu.z, pu.w};
+        *(lf2*)&win[2][r][c + 2] = (lf2){pv.z, pv.w};
+      }
+    }
   }
 }
 
 template <int NT_>
 __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
   const int ny = (int)a.ny, nx = (int)a.nx;
-  const S1Tiles tl = s1_tiles(ny, nx, a.f);
+  const S1Tiles tl = s1_tiles(ny, nx, a.f, a.march);
   const int b_ = (int)blockIdx.x;
-  int tr, tc;
-  const int flavour = s1_block_tile(tl, b_, &tr, &tc);
+  int tr, tc, ntile;
+  const int flavour = s1_block_tile(tl, b_, &tr, &tc, &ntile);
   if (flavour == 0) return;  // padding block
   const bool perim = flavour == 1;
   const int jb = tr * kTJ30;       // first owned output row
@@ -1654,8 +1673,12 @@ __global__ void __launch_bounds__(NT_) sw_step1t(SwArgs<float> a) {
   __shared__ S30Tile su, sv;
   __shared__ __attribute__((aligned(16))) S1Win win;
 
-  // pass 1 of a fast tile: every fill pair from the staged window
-  if (!perim) s1_fast_fill<NT_>(a, jb, cb, tid, win, su, sv);
+  // a segment of fast tiles: both passes of every tile, from the staged
+  // window
+  if (!perim) {
+    s1_fast_march<NT_>(a, jb, cb, ntile, tid, win, su, sv);
+    return;
+  }
 
   // pass 1 of a perimeter tile, vector: the stage-19 update of its fast
   // pairs, rows from global memory (sw_stage30t's fill loop minus the
@@ -1858,6 +1881,7 @@ static void sw_fill_args(SwArgs<T>& a, const SwLaunchParams& p) {
   a.ab_b = (T)p.ab_b;
   a.f = {p.south_open, p.north_open, p.west_open, p.east_open, p.east_wall,
          p.north_wall, p.x_wrap};
+  a.march = 1;  // sw_step1t's launch sets its own
 }
 
 // scalar stages: one cell per thread, 1-D grid of row-major column-chunk
@@ -1930,10 +1954,13 @@ SwStageStatus launch_sw_stage(int stage, const SwLaunchParams& p,
     case SW_STEP1_512:  // 512-thread blocks (single-round LDS fill)
     {
       if (is_double) return SW_STAGE_F32_ONLY;
-      const S1Tiles tl = s1_tiles((int)p.ny, (int)p.nx, a.f);
+      // fast tiles per block.  The default is 1, no march: no longer
+      // march measured faster (profiles/README.md, "Marching fast tiles")
+      a.march = p.march > 0 ? p.march : 1;
+      const S1Tiles tl = s1_tiles((int)p.ny, (int)p.nx, a.f, a.march);
       return stage == SW_STEP1
-                 ? f32(sw_step1t<256>, tl.nper_pad + tl.nfast)
-                 : f32(sw_step1t<512>, tl.nper_pad + tl.nfast, 512);
+                 ? f32(sw_step1t<256>, tl.nper_pad + tl.nseg)
+                 : f32(sw_step1t<512>, tl.nper_pad + tl.nseg, 512);
     }
     case SW_FUSED_FAST_RINGA:  // multi-rank: a real fe/fn strip exchange
                                // runs before SW_FUSED_RINGB

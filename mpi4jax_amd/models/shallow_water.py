@@ -233,6 +233,12 @@ class ShallowWater:
     # (equal up to FMA contraction inside the fused kernels).
     def _fused_flags(self):
         g = self.grid
+        # MPI4JAX_AMD_SW_MARCH: fast tiles per block of the single-launch
+        # step, as an optional 8th entry (unset = the launcher's default)
+        march = os.environ.get("MPI4JAX_AMD_SW_MARCH", "").strip()
+        return self._edge_flags(g) + ([int(march)] if march else [])
+
+    def _edge_flags(self, g):
         return [
             int(g.neighbor("south") is not None),
             int(g.neighbor("north") is not None),

@@ -85,7 +85,7 @@ def build_native(force=False, variant=""):
         objs.append(op)
         deps = [sp, CSRC / "kernels.h", CSRC / "halo_geom.h",
                 CSRC / "halo_types.h", CSRC / "krylov_reduce.h",
-                CSRC / "stencil_cells.h"]
+                CSRC / "stencil_cells.h", CSRC / "sw_tiles.h"]
         variant_flags = []
         if variant == "nofma" and src.endswith(".hip"):
             variant_flags = ["-ffp-contract=off"]
