@@ -1911,6 +1911,53 @@ void halo_zline_solve_nd(std::vector<at::Tensor> r, std::vector<at::Tensor> z,
                          cur_stream()));
 }
 
+// The tensors of a fused update beyond its geometry.
+struct ZlineUpdate {
+  const std::vector<at::Tensor>&x, &r, &p, &q, &z;
+  const at::Tensor &tables, &rz, &pq, &rz_old, &rr, &partials;
+};
+
+// What a fused update checks and enqueues after its geometry, for either
+// kernel's argument struct: the scalars, `partials` (two slots per block)
+// and the aliasing checks, the pointers into `a`, then `launch(stream)`
+// and the two finish launches.
+template <typename Args, typename Launch>
+void zline_update_run(const char* who, Args& a, unsigned blocks,
+                      const ZlineUpdate& u, Launch launch) {
+  const at::Device dev = u.x[0].device();
+  a.partials = krylov_partials(who, u.partials, dev, 2 * blocks);
+  a.num = krylov_scalar(who, "rz", u.rz, dev);
+  a.den = krylov_scalar(who, "pq", u.pq, dev);
+  double* old = krylov_scalar(who, "rz_old", u.rz_old, dev);
+  double* res_rr = krylov_scalar(who, "rr", u.rr, dev);
+  std::vector<at::Tensor> written(u.x), read(u.p);
+  written.insert(written.end(), u.r.begin(), u.r.end());
+  written.insert(written.end(), u.z.begin(), u.z.end());
+  read.insert(read.end(), u.q.begin(), u.q.end());
+  krylov_fields_disjoint(who, written, read);
+  const at::Tensor* small[6] = {&u.rz, &u.pq,       &u.rz_old,
+                                &u.rr, &u.partials, &u.tables};
+  const char* names[6] = {"rz", "pq", "rz_old", "rr", "partials", "tables"};
+  for (int i = 0; i < 6; ++i) {
+    krylov_no_overlap(who, *small[i], names[i], written);
+    for (int j = 0; j < i; ++j) {
+      krylov_no_overlap(who, *small[i], names[i], {*small[j]});
+    }
+  }
+  for (size_t k = 0; k < u.x.size(); ++k) {
+    a.p[k] = u.p[k].data_ptr();
+    a.q[k] = u.q[k].data_ptr();
+    a.x[k] = u.x[k].data_ptr();
+    a.r[k] = u.r[k].data_ptr();
+    a.z[k] = u.z[k].data_ptr();
+  }
+  hipStream_t stream = cur_stream();
+  HIP_CHECK(launch(stream));
+  HIP_CHECK(launch_krylov_finish(a.partials, blocks, res_rr, nullptr, stream));
+  HIP_CHECK(launch_krylov_finish(a.partials + blocks, blocks,
+                                 (double*)a.num, old, stream));
+}
+
 // The update step of line-preconditioned CG in one launch plus two finish
 // launches: alpha = rz / pq (0 when pq == 0), x += alpha p, r -= alpha q,
 // z = T^{-1} r; then rr = this rank's r . r, rz_old = rz and rz = this
@@ -1928,37 +1975,110 @@ void halo_zline_pcg_update_nd(
   unsigned blocks = 0;
   ZLineArgs a = zline_args(who, {&x, &r, &p, &q, &z}, levels, nz, ny, nx,
                            width, tables, periodic, lds_planes, &blocks);
-  const at::Device dev = x[0].device();
-  a.partials = krylov_partials(who, partials, dev, 2 * blocks);
-  a.num = krylov_scalar(who, "rz", rz, dev);
-  a.den = krylov_scalar(who, "pq", pq, dev);
-  double* old = krylov_scalar(who, "rz_old", rz_old, dev);
-  double* res_rr = krylov_scalar(who, "rr", rr, dev);
-  std::vector<at::Tensor> written(x), read(p);
-  written.insert(written.end(), r.begin(), r.end());
-  written.insert(written.end(), z.begin(), z.end());
-  read.insert(read.end(), q.begin(), q.end());
-  krylov_fields_disjoint(who, written, read);
-  const at::Tensor* small[6] = {&rz, &pq, &rz_old, &rr, &partials, &tables};
-  const char* names[6] = {"rz", "pq", "rz_old", "rr", "partials", "tables"};
-  for (int i = 0; i < 6; ++i) {
-    krylov_no_overlap(who, *small[i], names[i], written);
-    for (int j = 0; j < i; ++j) {
-      krylov_no_overlap(who, *small[i], names[i], {*small[j]});
-    }
-  }
-  for (size_t k = 0; k < x.size(); ++k) {
-    a.p[k] = p[k].data_ptr();
-    a.q[k] = q[k].data_ptr();
-    a.x[k] = x[k].data_ptr();
+  const int dt = dt_code(x[0]);
+  zline_update_run(
+      who, a, blocks, {x, r, p, q, z, tables, rz, pq, rz_old, rr, partials},
+      [&](hipStream_t s) {
+        return launch_zline(a, ZLINE_PCG_UPDATE, dt, blocks, s);
+      });
+}
+
+// ---- the same line solves by parallel cyclic reduction (zline_pcr.hip)
+
+// Field, geometry and table checks of the two entries below, as
+// zline_args; `cols` is the tile width C.
+ZLinePcrArgs zline_pcr_args(
+    const char* who, const std::vector<const std::vector<at::Tensor>*>& lists,
+    int64_t levels, int64_t nz, int64_t ny, int64_t nx, int64_t w,
+    const at::Tensor& tables, bool periodic, int64_t cols,
+    unsigned* blocks) {
+  unsigned unused = 0;
+  krylov_args(who, lists, levels, ny, nx, w, true, &unused);
+  const at::Tensor& f0 = (*lists[0])[0];
+  TORCH_CHECK(nz >= 1 && levels % nz == 0, who, ": nz = ", nz,
+              " does not divide ", levels, " levels");
+  TORCH_CHECK(!periodic || nz >= 3, who, ": periodic z needs nz >= 3, got ",
+              nz);
+  int64_t pcr_levels = 0;
+  while (((int64_t)1 << pcr_levels) < nz) ++pcr_levels;
+  const int64_t rows = 2 * pcr_levels + 2;
+  TORCH_CHECK(tables.is_cuda() && tables.device() == f0.device() &&
+                  tables.scalar_type() == f0.scalar_type() &&
+                  tables.is_contiguous() && tables.dim() == 2 &&
+                  tables.size(0) == rows && tables.size(1) == nz,
+              who, ": tables must be a contiguous (", rows, ", ", nz,
+              ") tensor of the fields' dtype on their device");
+  const int64_t per_col = 2 * nz * f0.element_size();
+  TORCH_CHECK_VALUE((cols == 8 || cols == 16 || cols == 32 || cols == 64) &&
+                        cols * per_col <= kZlineMaxLds,
+                    who, ": columns_per_block must be 8, 16, 32 or 64 and at "
+                    "most ", kZlineMaxLds / per_col, " at nz = ", nz,
+                    ", got ", cols);
+  const int64_t nf = (int64_t)lists[0]->size();
+  const int64_t columns = levels / nz;
+  const TileGrid tg =
+      tile_grid(who, ny, nx, w, 1, cols, nf * columns, "columns");
+  *blocks = tg.blocks;
+  ZLinePcrArgs a{};
+  a.tables = tables.data_ptr();
+  a.ny = ny;
+  a.nx = nx;
+  a.nz = (unsigned)nz;
+  a.columns = (unsigned)columns;
+  a.rows = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
+  a.levels = (unsigned)pcr_levels;
+  a.cols_log2 = cols == 8 ? 3 : cols == 16 ? 4 : cols == 32 ? 5 : 6;
+  a.w = (int)w;
+  a.periodic = periodic ? 1 : 0;
+  return a;
+}
+
+// ZLineSolver.solve with method="pcr": halo_zline_solve_nd by cyclic
+// reduction.
+void halo_zline_pcr_solve_nd(std::vector<at::Tensor> r,
+                             std::vector<at::Tensor> z, int64_t levels,
+                             int64_t nz, int64_t ny, int64_t nx,
+                             int64_t width, at::Tensor tables, bool periodic,
+                             int64_t columns_per_block) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_zline_pcr_solve_nd");
+  const char* who = "halo_zline_pcr_solve_nd";
+  unsigned blocks = 0;
+  ZLinePcrArgs a = zline_pcr_args(who, {&r, &z}, levels, nz, ny, nx, width,
+                                  tables, periodic, columns_per_block,
+                                  &blocks);
+  krylov_fields_disjoint(who, z, r);
+  krylov_no_overlap(who, tables, "tables", z);
+  for (size_t k = 0; k < r.size(); ++k) {
     a.r[k] = r[k].data_ptr();
     a.z[k] = z[k].data_ptr();
   }
-  hipStream_t stream = cur_stream();
-  HIP_CHECK(launch_zline(a, ZLINE_PCG_UPDATE, dt_code(x[0]), blocks, stream));
-  HIP_CHECK(launch_krylov_finish(a.partials, blocks, res_rr, nullptr, stream));
-  HIP_CHECK(launch_krylov_finish(a.partials + blocks, blocks,
-                                 (double*)a.num, old, stream));
+  HIP_CHECK(launch_zline_pcr(a, ZLINE_SOLVE, dt_code(r[0]), blocks,
+                             cur_stream()));
+}
+
+// halo_zline_pcg_update_nd with the line solve by cyclic reduction: the
+// same results in the same places, `partials` sized by this kernel's
+// blocks.
+void halo_zline_pcr_update_nd(
+    std::vector<at::Tensor> x, std::vector<at::Tensor> r,
+    std::vector<at::Tensor> p, std::vector<at::Tensor> q,
+    std::vector<at::Tensor> z, int64_t levels, int64_t nz, int64_t ny,
+    int64_t nx, int64_t width, at::Tensor tables, bool periodic,
+    int64_t columns_per_block, at::Tensor rz, at::Tensor pq,
+    at::Tensor rz_old, at::Tensor rr, at::Tensor partials) {
+  ROCTX_SCOPE("mpi4jax_amd::halo_zline_pcr_update_nd");
+  const char* who = "halo_zline_pcr_update_nd";
+  unsigned blocks = 0;
+  ZLinePcrArgs a =
+      zline_pcr_args(who, {&x, &r, &p, &q, &z}, levels, nz, ny, nx, width,
+                     tables, periodic, columns_per_block, &blocks);
+  const int dt = dt_code(x[0]);
+  zline_update_run(
+      who, a, blocks, {x, r, p, q, z, tables, rz, pq, rz_old, rr, partials},
+      [&](hipStream_t s) {
+        return launch_zline_pcr(a, ZLINE_PCG_UPDATE, dt, blocks, s);
+      });
 }
 
 // Native executor of HaloStencil.adjoint: halo_stencil_adjoint_sequence
@@ -2361,4 +2481,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_cg_direction_nd", &halo_cg_direction_nd);
   m.def("halo_zline_solve_nd", &halo_zline_solve_nd);
   m.def("halo_zline_pcg_update_nd", &halo_zline_pcg_update_nd);
+  m.def("halo_zline_pcr_solve_nd", &halo_zline_pcr_solve_nd);
+  m.def("halo_zline_pcr_update_nd", &halo_zline_pcr_update_nd);
 }

@@ -516,3 +516,64 @@ struct ZLineArgs {
 // kZlineMaxLds.  Returns the launch's status.
 hipError_t launch_zline(const ZLineArgs& a, int mode, int dt_code,
                         unsigned blocks, hipStream_t stream);
+
+// The same line solves by parallel cyclic reduction (zline_pcr.hip;
+// ZLineSolver with method="pcr"), for tall columns on planes too small to
+// fill the GPU with one thread per column.  T, the fields and the two
+// modes are those of ZLineArgs.
+//
+// `tables` is (2 L + 2, nz) in the field dtype, L = `levels` =
+// ceil(log2 nz), from the host's float64 reduction of T (of the
+// Sherman-Morrison matrix T' under periodic z) rounded once.  With lo, d,
+// up the rows of the matrix, lo_0 = up_{nz-1} = 0, level l has stride
+// s = 2^l and
+//   row l      alpha_k = -lo_k / d_{k-s}   (0 where k - s < 0)
+//   row L + l  gamma_k = -up_k / d_{k+s}   (0 where k + s >= nz)
+// and leaves lo'_k = alpha_k lo_{k-s}, up'_k = gamma_k up_{k+s},
+// d'_k = d_k + alpha_k up_{k-s} + gamma_k lo_{k+s} to the next level;
+//   row 2 L      inv_k = 1 / d_k after the last level
+//   row 2 L + 1  qs_k as in ZLineArgs (periodic only)
+// and tables[0][0], which no level reads, holds g under periodic z.
+//
+// A 256-thread block owns C = `cols` (8, 16, 32 or 64) consecutive interior
+// cells of one row of one column of one field: lane = t % C along x, and
+// thread t works on the planes k = t / C, t / C + 256 / C, ...  The block
+// index decodes, fastest first, to (tile x, row, column, field): `blocks` =
+// nf * columns * rows * tiles_x < 2^24, 32-bit; offsets into a field are
+// 64-bit.  Two buffers of nz * C values, [k][lane], live in
+// 2 * nz * C * sizeof(dtype) <= kZlineMaxLds bytes of dynamic LDS.  Per
+// cell:
+//   v_k = r_k;  per level  v'_k = v_k + alpha_k v_{k-s} + gamma_k v_{k+s},
+//   a neighbour outside 0..nz-1 neither read nor multiplied;
+//   s_k = v_k inv_k;  z_k = s_k, or under periodic z
+//   z_k = s_k - qs_k (s_0 + g s_{nz-1}).
+// The arithmetic of a cell does not depend on C.  Cells past the ragged
+// end of a row are neither read nor written.
+//
+// ZLINE_PCG_UPDATE: the load forms x + alpha p and rn = r - alpha q as
+// ZLineArgs says, stores both, adds double(rn)^2 to the thread's first sum
+// and reduces rn; the store re-reads the thread's own rn and adds
+// double(rn) * double(z_k) to its second sum.  A thread adds in ascending
+// k; then krylov_block_sum twice, into partials[b] and
+// partials[blocks + b].
+struct ZLinePcrArgs {
+  const void* p[kHaloMaxFields];  // update only
+  const void* q[kHaloMaxFields];  // update only
+  void* x[kHaloMaxFields];        // update only
+  void* r[kHaloMaxFields];        // solve: read;  update: read and written
+  void* z[kHaloMaxFields];
+  const void* tables;
+  const double* num;  // update: alpha = *num / *den, 0 when *den == 0
+  const double* den;
+  double* partials;   // update: 2 * blocks slots
+  long long ny, nx;
+  unsigned nz, columns, rows, tiles_x, levels, cols_log2;
+  int w, periodic;
+};
+
+// dt_code must be DT_F32 or DT_F64 (anything else launches nothing; the
+// caller checks), cols_log2 in 3..6, levels = ceil(log2 nz), nz >= 3 when
+// periodic, and the two buffers within kZlineMaxLds.  Returns the
+// launch's status.
+hipError_t launch_zline_pcr(const ZLinePcrArgs& a, int mode, int dt_code,
+                            unsigned blocks, hipStream_t stream);

@@ -18,9 +18,10 @@ finish launches after the reductions) when the fields live on the GPU:
 1. ``q = A p`` and ``pq = p . q`` — the step of ``StencilCG``, unchanged;
 2. ``alpha = rz / pq``; ``x += alpha p``; ``r -= alpha q``;
    ``z = M^{-1} r``; ``rr = r . r``; ``rz_old = rz``; ``rz = r . z`` on the
-   stored ``r`` and ``z`` — ONE launch of ``csrc/zline.hip``: the line
-   solve needs whole columns of the new ``r``, which the update produces
-   plane by plane;
+   stored ``r`` and ``z`` — ONE launch of ``csrc/zline.hip`` (or, with
+   ``line_method="pcr"``, of ``csrc/zline_pcr.hip``): the line solve
+   needs whole columns of the new ``r``, which the update produces plane
+   by plane;
 3. ``beta = rz / rz_old``; ``p = z + beta p`` — the direction kernel of
    ``StencilCG`` on ``z``.
 
@@ -38,9 +39,11 @@ class StencilPCG(StencilCG):
     """See the module docstring.  Build with
     ``HaloStencil3D.make_cg("zline")``."""
 
-    def __init__(self, stencil, _lds_planes=None):
+    def __init__(self, stencil, _lds_planes=None, line_method="thomas",
+                 _pcr_columns=None):
         super().__init__(stencil)
-        self.line_solver = stencil.make_line_solver(_lds_planes=_lds_planes)
+        self.line_solver = stencil.make_line_solver(
+            line_method, _lds_planes=_lds_planes, _pcr_columns=_pcr_columns)
         ex = stencil.exchanger
         # halo zero, never written
         self._z = [torch.zeros(ex.shape, dtype=ex.dtype, device=ex.device)

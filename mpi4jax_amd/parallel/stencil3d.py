@@ -155,21 +155,29 @@ class HaloStencil3D(HaloStencil):
         raise TypeError("make_chebyshev is 2-D only: the 3-D stencil has "
                         "no Chebyshev kernel yet")
 
-    def make_line_solver(self, _lds_planes=None):
+    def make_line_solver(self, method="thomas", _lds_planes=None,
+                         _pcr_columns=None):
         """A :class:`~.zline.ZLineSolver`: ``T^{-1}`` for the tridiagonal
         part ``T`` of this stencil along z (its ``(dz, 0, 0)`` weights).
+        ``method="thomas"``: one thread marches over each column;
+        ``"pcr"``: parallel cyclic reduction of a tile of columns in LDS,
+        for tall columns on small planes (``ValueError`` for any other
+        value, or for an ``nz`` whose columns do not fit in LDS).
         ``ValueError`` for a non-zero ``(+-2, 0, 0)`` weight or a ``T``
         whose factorisation meets a non-positive pivot; float32 and
         float64 only (``TypeError``)."""
         from .zline import ZLineSolver
 
-        return ZLineSolver(self, _lds_planes=_lds_planes)
+        return ZLineSolver(self, _lds_planes=_lds_planes, method=method,
+                           _pcr_columns=_pcr_columns)
 
-    def make_cg(self, preconditioner=None, _lds_planes=None):
+    def make_cg(self, preconditioner=None, line_method="thomas",
+                _lds_planes=None, _pcr_columns=None):
         """``preconditioner=None``: the :class:`~.cg.StencilCG` of
         ``HaloStencil.make_cg``.  ``"zline"``: a
         :class:`~.pcg.StencilPCG`, conjugate gradients preconditioned by
-        the exact vertical line solve of :meth:`make_line_solver`."""
+        the exact vertical line solve of :meth:`make_line_solver` with
+        ``method=line_method``."""
         if preconditioner is None:
             return super().make_cg()
         if preconditioner != "zline":
@@ -178,7 +186,8 @@ class HaloStencil3D(HaloStencil):
                 f"{preconditioner!r}")
         from .pcg import StencilPCG
 
-        return StencilPCG(self, _lds_planes=_lds_planes)
+        return StencilPCG(self, _lds_planes=_lds_planes,
+                          line_method=line_method, _pcr_columns=_pcr_columns)
 
     # ------------------------------------------------------------------
     def _native_args(self, ins, outs):

@@ -38,7 +38,32 @@ every product is exact.
 
 The march is serial in z: its parallelism is the number of columns,
 ``nfields * B * ny * nx``.  Very tall columns on very small horizontal
-grids leave the GPU few threads; there is no cyclic-reduction variant.
+grids leave the GPU few threads.
+
+``method="pcr"`` is for those: parallel cyclic reduction.  With ``lo``,
+``d``, ``up`` the rows of ``T`` (of ``T'`` under periodic z) and stride
+``s = 1, 2, 4, ...``, a level adds ``alpha_k = -lo_k / d_{k-s}`` times row
+``k - s`` and ``gamma_k = -up_k / d_{k+s}`` times row ``k + s`` to row
+``k``, which moves its off-diagonals out to distance ``2 s``:
+``lo'_k = alpha_k lo_{k-s}``, ``up'_k = gamma_k up_{k+s}``,
+``d'_k = d_k + alpha_k up_{k-s} + gamma_k lo_{k+s}``.  After ``levels =
+ceil(log2 nz)`` levels the matrix is diagonal.  ``T`` is the same for
+every column, so the host runs this once in float64 (``_pcr``, after
+``_thomas`` for its refusals, ``qs`` and ``g``; a ``d`` that is not
+positive and finite is refused in the same words) and rounds once; the
+executors only multiply:
+
+* per level: ``v'_k = v_k + alpha_k v_{k-s} + gamma_k v_{k+s}``, a
+  neighbour outside ``0..nz-1`` neither read nor multiplied;
+* ``s_k = v_k inv_k`` with ``inv_k = 1 / d_k`` of the last level, then the
+  periodic correction above.
+
+The native executor (``csrc/zline_pcr.hip``) gives ``columns_per_block``
+cells of one row, with all their planes, to a block that keeps two ``nz x
+columns_per_block`` buffers in LDS; the host takes the widest of 64, 32,
+16 and 8 that fits in LDS, and no wider than covers an interior row.  The
+Python executor slices over planes.  ``nz`` is limited to what fits at 8
+columns: 1023 in float32, 511 in float64.
 
 float32 and float64 only.
 """
@@ -53,11 +78,18 @@ from .cg import CG_DTYPES
 BLOCK = 256            # kZlineBlock of csrc/kernels.h
 TILE_Y, TILE_X = 4, 64  # kZlineTileY, kZlineTileX
 MAX_LDS = 65536 - 64   # kZlineMaxLds: 64 KiB less the reduction's slots
+PCR_COLUMNS = (8, 16, 32, 64)  # tile widths of csrc/zline_pcr.hip
 # A periodic T counts as singular when its Sherman-Morrison denominator is
 # within this many nz * eps64 of the terms it sums (see _thomas).  Over nz in
 # 3..70 the singular bands (-1, 2, -1) give at most 0.09 of these units and
 # the nearly singular (-1, 2 + 1e-6, -1) 5e8.
 _SINGULAR = 1024.0
+
+
+def _not_definite(k, pivot):
+    return ValueError(
+        f"the stencil is not positive definite along z: pivot {k} of "
+        f"its vertical tridiagonal part is {pivot}")
 
 
 def _thomas(nz, a, b, c, periodic):
@@ -70,11 +102,7 @@ def _thomas(nz, a, b, c, periodic):
     singular periodic ``T`` (``b = -(a + c)``) has ``den = 0`` in real
     arithmetic, which float64 returns as anything from 0 to about ``eps64``
     depending on ``nz``."""
-    def bad(k, pivot):
-        return ValueError(
-            f"the stencil is not positive definite along z: pivot {k} of "
-            f"its vertical tridiagonal part is {pivot}")
-
+    bad = _not_definite
     diag = [b] * nz
     gamma = -b
     if periodic:
@@ -106,11 +134,51 @@ def _thomas(nz, a, b, c, periodic):
     return inv, cp, qs, lo
 
 
+def _pcr(nz, a, b, c, periodic):
+    """The ``2 L + 2`` rows of the cyclic-reduction table as float64 lists:
+    ``L`` of alpha, ``L`` of gamma, inv and qs, ``L = ceil(log2 nz)``.
+
+    ``_thomas`` runs first, so every refusal of the Thomas path is made
+    here in the same words; ``qs`` and ``g`` are its own.  A reduced
+    diagonal entry that is not positive and finite raises the same
+    ``ValueError``.  Under periodic z ``alpha[0][0]``, which no level
+    reads, holds ``g``."""
+    _, _, qs, lo_t = _thomas(nz, a, b, c, periodic)
+    d = [b] * nz
+    if periodic:
+        gamma = -b  # T' of _thomas
+        d[0], d[-1] = b - gamma, b - a * c / gamma
+    lo, up = [0.0] + [a] * (nz - 1), [c] * (nz - 1) + [0.0]
+    levels = (nz - 1).bit_length()
+    alphas, gammas = [], []
+    for s in (1 << level for level in range(levels)):
+        al = [-lo[k] / d[k - s] if k >= s else 0.0 for k in range(nz)]
+        ga = [-up[k] / d[k + s] if k + s < nz else 0.0 for k in range(nz)]
+        nd = [d[k] + (al[k] * up[k - s] if k >= s else 0.0)
+              + (ga[k] * lo[k + s] if k + s < nz else 0.0)
+              for k in range(nz)]
+        for k, pivot in enumerate(nd):
+            if not (math.isfinite(pivot) and pivot > 0.0):
+                raise _not_definite(k, pivot)
+        lo = [al[k] * lo[k - s] if k >= s else 0.0 for k in range(nz)]
+        up = [ga[k] * up[k + s] if k + s < nz else 0.0 for k in range(nz)]
+        d = nd
+        alphas.append(al)
+        gammas.append(ga)
+    if periodic:
+        alphas[0][0] = lo_t[0]
+    return alphas + gammas + [[1.0 / v for v in d], qs]
+
+
 class ZLineSolver:
     """See the module docstring.  Build with
     ``HaloStencil3D.make_line_solver``."""
 
-    def __init__(self, stencil, _lds_planes=None):
+    def __init__(self, stencil, _lds_planes=None, method="thomas",
+                 _pcr_columns=None):
+        if method not in ("thomas", "pcr"):
+            raise ValueError(
+                f"method must be 'thomas' or 'pcr', got {method!r}")
         if stencil.dtype not in CG_DTYPES:
             raise TypeError(
                 f"line solves support float32 and float64, the stencil was "
@@ -129,9 +197,23 @@ class ZLineSolver:
         self._periodic = (stencil.z_boundary == "periodic"
                           and (a != 0.0 or c != 0.0))
         ex = stencil.exchanger
-        self._tables = torch.tensor(
-            _thomas(nz, a, b, c, self._periodic), dtype=torch.float64).to(
-                stencil.acc_dtype).to(ex.device)
+        self._method = method
+        self._partials = self._levels = self._cols = None
+        rows =(_pcr if method == "pcr" else _thomas)(
+            nz, a, b, c, self._periodic)
+        self._tables = torch.tensor(rows, dtype=torch.float64).to(
+            stencil.acc_dtype).to(ex.device)
+        if method == "pcr":
+            if _lds_planes is not None:
+                raise ValueError(
+                    "_lds_planes belongs to method='thomas': under 'pcr' "
+                    "every plane lives in LDS")
+            self._levels = (nz - 1).bit_length()
+            self._lds_planes = nz
+            self._cols = self._pick_columns(_pcr_columns)
+            return
+        if _pcr_columns is not None:
+            raise ValueError("_pcr_columns belongs to method='pcr'")
         most = MAX_LDS // (BLOCK * ex.dtype.itemsize)
         if _lds_planes is None:
             _lds_planes = min(nz, most)
@@ -142,7 +224,35 @@ class ZLineSolver:
                 f"_lds_planes must be an int in 0..{min(nz, most)}, got "
                 f"{_lds_planes!r}")
         self._lds_planes = _lds_planes
-        self._partials = None
+
+    def _pick_columns(self, forced):
+        """The tile width ``C`` of the cyclic-reduction kernel: the largest
+        of ``PCR_COLUMNS`` whose two ``nz x C`` buffers fit in LDS, and no
+        more than the smallest that covers an interior row."""
+        st = self.stencil
+        ex = st.exchanger
+        per_col = 2 * st.nz * ex.dtype.itemsize
+        fits = [c for c in PCR_COLUMNS if c * per_col <= MAX_LDS]
+        if not fits:
+            raise ValueError(
+                f"method='pcr' keeps two buffers of nz x {PCR_COLUMNS[0]} "
+                f"{ex.dtype} values in LDS: nz = {st.nz} exceeds the largest "
+                f"nz of {MAX_LDS // (2 * PCR_COLUMNS[0] * ex.dtype.itemsize)}")
+        if forced is None:
+            width = ex.nx - 2 * st.width
+            cover = [c for c in PCR_COLUMNS if c >= width]
+            return min(fits[-1], cover[0] if cover else PCR_COLUMNS[-1])
+        if (isinstance(forced, bool) or not isinstance(forced, int)
+                or forced not in fits):
+            raise ValueError(
+                f"_pcr_columns must be one of {fits} at nz = {st.nz}, got "
+                f"{forced!r}")
+        return forced
+
+    @property
+    def method(self):
+        """``"thomas"`` or ``"pcr"``."""
+        return self._method
 
     @property
     def bands(self):
@@ -152,13 +262,29 @@ class ZLineSolver:
     @property
     def lds_planes(self):
         """Planes of the forward sweep that the native kernel keeps in
-        LDS; the planes above go through the output array."""
+        LDS; the planes above go through the output array.  Under
+        ``"pcr"`` every plane lives in LDS: ``nz``."""
         return self._lds_planes
 
     @property
+    def levels(self):
+        """The reduction's levels under ``"pcr"``, ``ceil(log2 nz)``; None
+        under ``"thomas"``."""
+        return self._levels
+
+    @property
+    def columns_per_block(self):
+        """The cells of one row that a block of the ``"pcr"`` kernel owns;
+        None under ``"thomas"``."""
+        return self._cols
+
+    @property
     def tables(self):
-        """The ``(4, nz)`` device tensor of ``inv``, ``cp``, ``qs`` and
-        ``lo`` in ``Acc`` (``lo[0]`` holds ``g``)."""
+        """``"thomas"``: the ``(4, nz)`` device tensor of ``inv``, ``cp``,
+        ``qs`` and ``lo`` in ``Acc`` (``lo[0]`` holds ``g``).  ``"pcr"``:
+        the ``(2 levels + 2, nz)`` tensor of the ``alpha`` rows, the
+        ``gamma`` rows, ``inv`` and ``qs`` (``alpha[0][0]`` holds ``g``
+        under periodic z)."""
         return self._tables
 
     def solve(self, *fields, out=None):
@@ -177,7 +303,8 @@ class ZLineSolver:
         st = self.stencil
         ex = st.exchanger
         return (ex.levels, st.nz, ex.ny, ex.nx, st.width, self._tables,
-                self._periodic, self._lds_planes)
+                self._periodic,
+                self._cols if self._method == "pcr" else self._lds_planes)
 
     def _partials_buf(self):
         """Two float64 slots per block of the native kernel's grid."""
@@ -185,8 +312,9 @@ class ZLineSolver:
             st = self.stencil
             ex = st.exchanger
             w = st.width
-            tiles = (-(-(ex.ny - 2 * w) // TILE_Y)
-                     * -(-(ex.nx - 2 * w) // TILE_X))
+            ty, tx = ((1, self._cols) if self._method == "pcr"
+                      else (TILE_Y, TILE_X))
+            tiles = -(-(ex.ny - 2 * w) // ty) * -(-(ex.nx - 2 * w) // tx)
             self._partials = torch.empty(
                 2 * ex.nfields * (ex.levels // st.nz) * tiles,
                 dtype=torch.float64, device=ex.device)
@@ -196,7 +324,9 @@ class ZLineSolver:
         if self.stencil._native():
             from .._backend import rccl
 
-            rccl.ext().halo_zline_solve_nd(list(rs), list(zs), *self._geom())
+            entry = ("halo_zline_pcr_solve_nd" if self._method == "pcr"
+                     else "halo_zline_solve_nd")
+            getattr(rccl.ext(), entry)(list(rs), list(zs), *self._geom())
         else:
             for r, z in zip(rs, zs):
                 self._columns(z).copy_(self._solve_py(self._columns(r)))
@@ -211,6 +341,21 @@ class ZLineSolver:
 
     def _solve_py(self, r):
         nz = self.stencil.nz
+        if self._method == "pcr":
+            tab, lv = self._tables, self._levels
+            v = r
+            for level in range(lv):  # 2^level < nz: both slices non-empty
+                s = 1 << level
+                nxt = v.clone()
+                nxt[:, s:] += tab[level, s:, None, None] * v[:, :nz - s]
+                nxt[:, :nz - s] += (tab[lv + level, :nz - s, None, None]
+                                    * v[:, s:])
+                v = nxt
+            v = v * tab[2 * lv, :, None, None]
+            if self._periodic:
+                fac = v[:, 0] + tab[0, 0] * v[:, nz - 1]
+                v = v - tab[2 * lv + 1, :, None, None] * fac[:, None]
+            return v
         inv, cp, qs, lo = self._tables
         y = torch.empty_like(r)
         y[:, 0] = r[:, 0] * inv[0]
@@ -232,7 +377,9 @@ class ZLineSolver:
         if st._native():
             from .._backend import rccl
 
-            rccl.ext().halo_zline_pcg_update_nd(
+            entry = ("halo_zline_pcr_update_nd" if self._method == "pcr"
+                     else "halo_zline_pcg_update_nd")
+            getattr(rccl.ext(), entry)(
                 x, r, p, q, z, *self._geom(), rz, pq, rz_old, rr,
                 self._partials_buf())
             return

@@ -79,7 +79,8 @@ def build_native(force=False, variant=""):
     objs = []
     for src in ["kernels.hip", "shallow_water.hip", "halo.hip",
                 "stencil.hip", "krylov.hip", "varstencil.hip",
-                "stencil3d.hip", "zline.hip", "bridge.cpp"]:
+                "stencil3d.hip", "zline.hip", "zline_pcr.hip",
+                "bridge.cpp"]:
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
