@@ -2081,6 +2081,196 @@ void halo_zline_pcr_update_nd(
       });
 }
 
+// ---- per-column tridiagonal solves (parallel/ztridiag.ColumnTridiagonal,
+// ztridiag.hip)
+
+// Geometry checks of the three entries below and the arguments they share;
+// `groups` is the number of tile grids.  Raises before anything is
+// enqueued.  No exchange: every entry runs on the current stream.
+ZTridiagArgs ztridiag_args(const char* who, int64_t nz, int64_t ny,
+                           int64_t nx, int64_t w, int64_t groups,
+                           unsigned* blocks) {
+  TORCH_CHECK_VALUE(nz >= 1 && w >= 0 && ny > 2 * w && nx > 2 * w, who,
+                    ": bad geometry: nz ", nz, ", ny ", ny, ", nx ", nx,
+                    ", width ", w, " (nz >= 1, width >= 0 and a non-empty "
+                    "interior)");
+  TORCH_CHECK_VALUE(nz < ((int64_t)1 << 31) && ny < ((int64_t)1 << 31) &&
+                        nx < ((int64_t)1 << 31),
+                    who, ": extents must be below 2^31");
+  const TileGrid tg = tile_grid(who, ny, nx, w, kZlineTileY, kZlineTileX,
+                               groups, "right-hand-side group(s)");
+  *blocks = tg.blocks;
+  ZTridiagArgs a{};
+  a.ny = ny;
+  a.nx = nx;
+  a.nz = (unsigned)nz;
+  a.tiles_y = tg.tiles_y;
+  a.tiles_x = tg.tiles_x;
+  a.w = (int)w;
+  return a;
+}
+
+// A (planes, ny, nx) tensor of the solver: on the GPU, contiguous, real
+// float32 or float64.
+void ztridiag_tensor(const char* who, const char* name, const at::Tensor& t,
+                     int64_t planes, int64_t ny, int64_t nx) {
+  const auto st = t.scalar_type();
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  (st == at::kFloat || st == at::kDouble),
+              who, ": ", name, " must be a contiguous float32 or float64 "
+              "tensor on the GPU");
+  TORCH_CHECK_VALUE(t.numel() == planes * ny * nx, who, ": ", name, " has ",
+                    t.numel(), " elements, expected ", planes, " x ", ny,
+                    " x ", nx);
+}
+
+// The three bands: (nz, ny, nx), one dtype, one device.  Returns their
+// dtype code.
+int ztridiag_bands(const char* who, ZTridiagArgs& a, const at::Tensor& lower,
+                   const at::Tensor& diag, const at::Tensor& upper) {
+  const at::Tensor* band[3] = {&lower, &diag, &upper};
+  const char* names[3] = {"lower", "diag", "upper"};
+  for (int i = 0; i < 3; ++i) {
+    ztridiag_tensor(who, names[i], *band[i], a.nz, a.ny, a.nx);
+    TORCH_CHECK(band[i]->scalar_type() == lower.scalar_type() &&
+                    band[i]->device() == lower.device(),
+                who, ": ", names[i], " must have the dtype and device of "
+                "lower");
+  }
+  a.lower = lower.data_ptr();
+  a.diag = diag.data_ptr();
+  a.upper = upper.data_ptr();
+  return dt_code(lower);
+}
+
+// Right-hand sides and outputs of the two solves, R and lds_planes (`slots`
+// stash values per plane and thread); fills the field pointers of `a`.
+void ztridiag_fields(const char* who, ZTridiagArgs& a,
+                     const std::vector<at::Tensor>& r,
+                     const std::vector<at::Tensor>& x, int64_t batch,
+                     int64_t lds_planes, int64_t slots,
+                     const at::Device& dev) {
+  const int64_t nf = (int64_t)r.size();
+  TORCH_CHECK_VALUE(1 <= nf && nf <= kHaloMaxFields, who, ": 1..",
+                    kHaloMaxFields, " fields supported, got ", nf);
+  TORCH_CHECK_VALUE((int64_t)x.size() == nf, who, ": ", nf,
+                    " right-hand side(s) but ", x.size(), " output(s)");
+  const auto st = r[0].scalar_type();
+  for (int64_t k = 0; k < nf; ++k) {
+    ztridiag_tensor(who, "a right-hand side", r[k], batch * a.nz, a.ny, a.nx);
+    ztridiag_tensor(who, "an output", x[k], batch * a.nz, a.ny, a.nx);
+    TORCH_CHECK(r[k].scalar_type() == st && x[k].scalar_type() == st &&
+                    r[k].device() == dev && x[k].device() == dev,
+                who, ": field ", k, " differs in dtype or device");
+    a.r[k] = r[k].data_ptr();
+    a.x[k] = x[k].data_ptr();
+  }
+  krylov_fields_disjoint(who, x, r);
+  const int64_t per_plane = slots * kZlineBlock * r[0].element_size();
+  TORCH_CHECK_VALUE(0 <= lds_planes && lds_planes <= a.nz &&
+                        lds_planes * per_plane <= kZlineMaxLds,
+                    who, ": lds_planes must be in 0..min(nz, ",
+                    kZlineMaxLds / per_plane, "), got ", lds_planes);
+  a.batch = (unsigned)batch;
+  a.nrhs = (unsigned)(nf * batch);
+  a.lds_planes = (unsigned)lds_planes;
+}
+
+int64_t ztridiag_groups(const char* who, int64_t nf, int64_t batch,
+                        int64_t rhs_per_thread) {
+  TORCH_CHECK_VALUE(rhs_per_thread == 1 || rhs_per_thread == 2 ||
+                        rhs_per_thread == 4,
+                    who, ": rhs_per_thread must be 1, 2 or 4, got ",
+                    rhs_per_thread);
+  TORCH_CHECK_VALUE(batch >= 1 && batch < ((int64_t)1 << 31) / 8, who,
+                    ": bad batch ", batch);
+  return (nf * batch + rhs_per_thread - 1) / rhs_per_thread;
+}
+
+// ColumnTridiagonal.set_bands: factors <- bands; block b leaves its
+// smallest pivot and that pivot's plane in status[b].
+void ztridiag_factor_nd(at::Tensor lower, at::Tensor diag, at::Tensor upper,
+                        at::Tensor factors, at::Tensor status, int64_t nz,
+                        int64_t ny, int64_t nx, int64_t width) {
+  ROCTX_SCOPE("mpi4jax_amd::ztridiag_factor_nd");
+  const char* who = "ztridiag_factor_nd";
+  unsigned blocks = 0;
+  ZTridiagArgs a = ztridiag_args(who, nz, ny, nx, width, 1, &blocks);
+  const int band = ztridiag_bands(who, a, lower, diag, upper);
+  ztridiag_tensor(who, "factors", factors, 3 * nz, ny, nx);
+  TORCH_CHECK(factors.device() == lower.device(), who,
+              ": factors must live on the bands' device");
+  TORCH_CHECK(status.is_cuda() && status.device() == lower.device() &&
+                  status.scalar_type() == at::kDouble &&
+                  status.is_contiguous() &&
+                  status.numel() == 2 * (int64_t)blocks,
+              who, ": status must be a contiguous float64 tensor of ",
+              2 * (int64_t)blocks, " elements on the bands' device");
+  krylov_no_overlap(who, status, "status", {factors});
+  krylov_fields_disjoint(who, {factors}, {lower, diag, upper});
+  a.factors = factors.data_ptr();
+  a.status = (double*)status.data_ptr();
+  HIP_CHECK(launch_ztridiag(a, ZTRIDIAG_FACTOR, dt_code(factors), band, 1,
+                            blocks, cur_stream()));
+}
+
+// ColumnTridiagonal.solve: x = T^{-1} r from the stored factors; the halo
+// of x is not written.
+void ztridiag_solve_nd(std::vector<at::Tensor> r, std::vector<at::Tensor> x,
+                       at::Tensor factors, int64_t batch, int64_t nz,
+                       int64_t ny, int64_t nx, int64_t width,
+                       int64_t rhs_per_thread, int64_t lds_planes) {
+  ROCTX_SCOPE("mpi4jax_amd::ztridiag_solve_nd");
+  const char* who = "ztridiag_solve_nd";
+  unsigned blocks = 0;
+  const int64_t groups =
+      ztridiag_groups(who, (int64_t)r.size(), batch, rhs_per_thread);
+  ZTridiagArgs a = ztridiag_args(who, nz, ny, nx, width, groups, &blocks);
+  ztridiag_tensor(who, "factors", factors, 3 * nz, ny, nx);
+  ztridiag_fields(who, a, r, x, batch, lds_planes, rhs_per_thread,
+                  factors.device());
+  TORCH_CHECK(factors.scalar_type() == r[0].scalar_type(), who,
+              ": factors must have the fields' dtype");
+  krylov_no_overlap(who, factors, "factors", x);
+  a.factors = factors.data_ptr();
+  HIP_CHECK(launch_ztridiag(a, ZTRIDIAG_SOLVE, dt_code(r[0]), DT_F32,
+                            (int)rhs_per_thread, blocks, cur_stream()));
+}
+
+// ColumnTridiagonal.solve_bands: factorise and solve in one launch.
+// `work` holds cp of the planes above lds_planes, one copy per group.
+void ztridiag_solve_bands_nd(at::Tensor lower, at::Tensor diag,
+                             at::Tensor upper, std::vector<at::Tensor> r,
+                             std::vector<at::Tensor> x, at::Tensor work,
+                             int64_t batch, int64_t nz, int64_t ny,
+                             int64_t nx, int64_t width,
+                             int64_t rhs_per_thread, int64_t lds_planes) {
+  ROCTX_SCOPE("mpi4jax_amd::ztridiag_solve_bands_nd");
+  const char* who = "ztridiag_solve_bands_nd";
+  unsigned blocks = 0;
+  const int64_t groups =
+      ztridiag_groups(who, (int64_t)r.size(), batch, rhs_per_thread);
+  ZTridiagArgs a = ztridiag_args(who, nz, ny, nx, width, groups, &blocks);
+  const int band = ztridiag_bands(who, a, lower, diag, upper);
+  ztridiag_fields(who, a, r, x, batch, lds_planes, rhs_per_thread + 1,
+                  lower.device());
+  for (const at::Tensor* b : {&lower, &diag, &upper}) {
+    krylov_no_overlap(who, *b, "a band", x);
+  }
+  if (lds_planes < nz) {
+    ztridiag_tensor(who, "work", work, groups * (nz - lds_planes), ny, nx);
+    TORCH_CHECK(work.scalar_type() == r[0].scalar_type() &&
+                    work.device() == lower.device(),
+                who, ": work must have the fields' dtype and device");
+    krylov_fields_disjoint(who, {work}, {lower, diag, upper});
+    krylov_fields_disjoint(who, {work}, r);
+    krylov_no_overlap(who, work, "work", x);
+    a.work = work.data_ptr();
+  }
+  HIP_CHECK(launch_ztridiag(a, ZTRIDIAG_SOLVE_BANDS, dt_code(r[0]), band,
+                            (int)rhs_per_thread, blocks, cur_stream()));
+}
+
 // Native executor of HaloStencil.adjoint: halo_stencil_adjoint_sequence
 // with the stencil kernel's transposed mode.
 void halo_stencil_adjoint_nd(std::vector<at::Tensor> gouts,
@@ -2483,4 +2673,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_zline_pcg_update_nd", &halo_zline_pcg_update_nd);
   m.def("halo_zline_pcr_solve_nd", &halo_zline_pcr_solve_nd);
   m.def("halo_zline_pcr_update_nd", &halo_zline_pcr_update_nd);
+  m.def("ztridiag_factor_nd", &ztridiag_factor_nd);
+  m.def("ztridiag_solve_nd", &ztridiag_solve_nd);
+  m.def("ztridiag_solve_bands_nd", &ztridiag_solve_bands_nd);
 }

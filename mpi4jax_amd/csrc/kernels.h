@@ -577,3 +577,74 @@ struct ZLinePcrArgs {
 // launch's status.
 hipError_t launch_zline_pcr(const ZLinePcrArgs& a, int mode, int dt_code,
                             unsigned blocks, hipStream_t stream);
+
+// Per-column tridiagonal solves of parallel/ztridiag.ColumnTridiagonal
+// (ztridiag.hip).  Every interior (j, i) has a system of its own along z:
+// row k is l_k x_{k-1} + d_k x_k + u_k x_{k+1} with the bands `lower`,
+// `diag`, `upper`, three contiguous (nz, ny, nx) tensors of one dtype
+// (band_code: DT_F32 or DT_F64); l_0 and u_{nz-1} are never used and z is
+// closed.  Only interior cells of any tensor are read or written.
+//
+// The factorisation runs in float64 whatever the dtypes:
+//   pivot_0 = d_0,  pivot_k = d_k - l_k cp_{k-1},
+//   inv_k = 1 / pivot_k,  cp_k = u_k inv_k
+// and inv, cp and lo = l are rounded once to the field dtype.  `factors`
+// is (3, nz, ny, nx) in the field dtype, in the order inv, cp, lo.
+//
+// A right-hand side is one (field, batch column) pair, entry s = field *
+// batch + column of nrhs = nf * batch; a field is `batch` (nz, ny, nx)
+// columns.  A thread owns one interior (j, i) and carries R =
+// rhs_per_thread (1, 2 or 4) consecutive entries through one march over z;
+// a 256-thread block owns kZlineTileY x kZlineTileX cells, lanes along x.
+// The block index decodes, fastest first, to (tile x, tile y, group of R
+// entries): `blocks` = ceil(nrhs / R) * tiles_y * tiles_x < 2^24, 32-bit;
+// offsets into a tensor are 64-bit.  Per entry, in the field dtype:
+//   forward, k = 0 .. nz-1:  y_0 = r_0 inv_0,
+//                            y_k = (r_k - lo_k y_{k-1}) inv_k
+//   back, k = nz-1 .. 0:     x_{nz-1} = y_{nz-1},  x_k = y_k - cp_k x_{k+1}
+// and what an entry computes does not depend on R.  Entries past nrhs in
+// the last group are not touched.
+//
+// ZTRIDIAG_FACTOR: bands -> factors, one thread per cell, blocks = tiles_y
+// * tiles_x.  Block b also stores status[2 b] = the smallest pivot its
+// columns saw, a pivot that is not finite counting as -inf and a column
+// counting up to and including its first pivot that is not positive, and
+// status[2 b + 1] = that pivot's plane (the lower plane on a tie).  Every
+// tile holds an interior column.  Plain stores, no atomics.
+// ZTRIDIAG_SOLVE: x = T^{-1} r from `factors`.  y_k of the planes
+// k < lds_planes lives in dynamic LDS, slot (k * R + j) * 256 + thread for
+// entry j of the group, of the planes above in x[k] itself:
+// lds_planes * R * 256 * sizeof(dtype) <= kZlineMaxLds.
+// ZTRIDIAG_SOLVE_BANDS: the same from the bands, factorised on the way up
+// by the same float64 recurrence and rounded the same way, so the result
+// is that of FACTOR + SOLVE bit for bit; no pivot is looked at.  The
+// stash has R + 1 slots per plane, the last for cp_k: lds_planes *
+// (R + 1) * 256 * sizeof(dtype) <= kZlineMaxLds; cp_k of the planes above
+// goes to `work`, (groups, nz - lds_planes, ny, nx) in the field dtype.
+// x aliases no other tensor.
+enum ZTridiagOp : int {
+  ZTRIDIAG_FACTOR = 0,
+  ZTRIDIAG_SOLVE = 1,
+  ZTRIDIAG_SOLVE_BANDS = 2,
+};
+
+struct ZTridiagArgs {
+  const void* r[kHaloMaxFields];  // solves
+  void* x[kHaloMaxFields];        // solves
+  const void* lower;              // FACTOR, SOLVE_BANDS
+  const void* diag;
+  const void* upper;
+  void* factors;   // FACTOR: written;  SOLVE: read
+  void* work;      // SOLVE_BANDS with lds_planes < nz
+  double* status;  // FACTOR: two slots per block
+  long long ny, nx;
+  unsigned nz, batch, nrhs, tiles_y, tiles_x, lds_planes;
+  int w;
+};
+
+// dt_code must be DT_F32 or DT_F64, and so must band_code unless op is
+// ZTRIDIAG_SOLVE (anything else launches nothing; the caller checks);
+// rhs_per_thread 1, 2 or 4 for the solves.  Returns the launch's status.
+hipError_t launch_ztridiag(const ZTridiagArgs& a, int op, int dt_code,
+                           int band_code, int rhs_per_thread,
+                           unsigned blocks, hipStream_t stream);

@@ -24,6 +24,8 @@ from .zline import ZLineSolver  # noqa: F401
 from . import zline  # noqa: F401
 from .pcg import StencilPCG  # noqa: F401
 from . import pcg  # noqa: F401
+from .ztridiag import ColumnTridiagonal  # noqa: F401
+from . import ztridiag  # noqa: F401
 from .ddp import average_gradients  # noqa: F401
 from .tp import (  # noqa: F401
     ColumnParallelLinear,

@@ -232,6 +232,27 @@ class CartesianGrid:
             z_boundary=z_boundary, _force_remote=_force_remote,
             _z_chunk=_z_chunk)
 
+    def make_tridiagonal_solver(self, shape, dtype, device, lower, diag,
+                                upper, nfields=1, width=0,
+                                _rhs_per_thread=None, _lds_planes=None):
+        """Build a :class:`~.ztridiag.ColumnTridiagonal`: one tridiagonal
+        system along z per interior ``(j, i)`` of ``nfields`` fields of
+        shape ``(..., nz, ny, nx)``, with the real ``(nz, ny, nx)`` bands
+        ``lower``, ``diag`` and ``upper`` shared by every batch column and
+        field.  ``width >= 0`` halo cells per side in y and x are neither
+        read nor written; nothing is communicated.  ``solve`` uses the
+        bands factorised here or by ``set_bands``; ``solve_bands`` takes
+        new bands with every call.  ``_rhs_per_thread`` (1, 2 or 4) and
+        ``_lds_planes`` (``0..nz``, clipped to what fits) are test hooks
+        of the native kernels; results do not depend on them.
+        """
+        from .ztridiag import ColumnTridiagonal
+
+        return ColumnTridiagonal(
+            self, shape, dtype, device, lower, diag, upper, nfields=nfields,
+            width=width, _rhs_per_thread=_rhs_per_thread,
+            _lds_planes=_lds_planes)
+
     def _halo_exchange_impl(self, out):
         # imported here to avoid a circular import at package init
         from ..ops.sendrecv import sendrecv

@@ -80,7 +80,7 @@ def build_native(force=False, variant=""):
     for src in ["kernels.hip", "shallow_water.hip", "halo.hip",
                 "stencil.hip", "krylov.hip", "varstencil.hip",
                 "stencil3d.hip", "zline.hip", "zline_pcr.hip",
-                "bridge.cpp"]:
+                "ztridiag.hip", "bridge.cpp"]:
         sp = CSRC / src
         op = build_dir / (src.replace(".", "_") + ".o")
         objs.append(op)
